@@ -1,6 +1,6 @@
 """Benchmark of the V-FloodNet video-segmentation hot loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One *step* = one frame of ``test_video_seg.py:105-116``: bicubic resize (identity at 480p) -> ``segment`` ->
 object softmax -> ``memorize`` -> ``FeatureBank.update`` -> resize+argmax -> largest-component filter -> label D2H,
@@ -11,16 +11,28 @@ Workload (BASELINE.json config C2, fp32): the **100-frame 480x854 clip**, whatev
   * ``--steps K < 99``: the clip still runs from its first frame; frames ``1 .. s-1`` are an untimed pre-roll
     (they build the bank exactly as the reference loop would), the K frames ``s .. s+K-1`` are timed -- ``s`` is chosen
     so that the mean bank size of the timed frames equals the full-clip mean (the memory read and the bank update
-    cost grows with the bank) -- and the clip is then finished untimed.  ``full_clip_fps`` reports all 99 iterations.
+    cost grows with the bank).  With ``--full`` the clip is then finished untimed and ``full_clip_fps`` reports all
+    99 iterations.
 ``--warmup W`` steps on a throw-away bank precede everything (the contract's warm-up; repeated until the device has
 been busy for ``--min-warm-s`` so the timed region never starts on an idle-clocked GPU).
+
+A plain run does only what the headline needs: set-up, warm-up, pre-roll, the K timed steps (no instrumented frames
+among them), ``--dump-outputs DIR`` if given, the line.  ``--dump-outputs DIR`` writes what the loop handed its caller
+after the LAST timed step: ``DIR/labels.npy`` (float32 [H0, W0], the post-processed label map of rank 0's clip) and
+``DIR/bank_sizes.npy`` (float64 [objects], live bank entries per object after that step); inputs are seeded, so two
+builds can be compared output for output.
+
+``--full`` adds everything else the line can carry (as every run did before the option existed): the rest of the
+clip and ``full_clip_fps`` / ``value_ci``, the ``sustained`` rate past the clip, HIP-event brackets on sampled frames
+of the timed window (``roofline``, ``memory_read``; those frames run eagerly, so `value` includes their cost), the CPU
+oracle baseline and the parity checks below.  Without it those fields are null.
 
 ``--gpus N``: every rank runs its own clip (seed = rank + 1, weak scaling, no collective on the data path) and the
 per-clip label masks are exchanged with one RCCL all-gather inside the timed bracket (config C4).  Under
 ``torch.distributed.run`` the ranks come from the environment; without it (``WORLD_SIZE`` unset) this script starts
 the N ranks itself as child processes *before anything touches the GPU* and rank 0 prints the line.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields plus (``--full``)
   roofline      the dominant kernel (f32-MFMA implicit-GEMM conv): algorithmic FLOP / HIP-event time
                 measured on sampled frames of the timed region, against the 157.3 TFLOP/s f32 matrix peak
   memory_read   the fused memory read of the sampled frames: algorithmic FLOP (scores counted once) / HIP-event time
@@ -48,6 +60,7 @@ DTYPES = {'fp32': 'f32', 'bf16': 'bf16 operands, f32 accumulate/storage', 'bf16x
 WORKLOADS = {'C2': (480, 854, 1), 'C3': (720, 1280, 5), 'C5': (1080, 1920, 1)}      # H0, W0, memorize every n-th frame
 CLIP_FRAMES = 100                     # BASELINE.json configs[1]: "100-frame 480p synthetic clip"
 PROFILE_ROUND = 'r06'
+DUMP_MAX_BYTES = 64 << 20
 
 
 def miou(a, b):
@@ -93,6 +106,16 @@ class ConvTimer:
             d[1] += ms
             d[2] += 1
         return per
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs``: every array as ``dirname/<name>.npy`` (float32 / float64, 64 MB at most in all)."""
+    import numpy as np
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        raise ValueError(f'--dump-outputs: {sum(a.nbytes for a in arrays.values())} bytes, more than {DUMP_MAX_BYTES}')
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def parse_args(argv=None):
@@ -147,6 +170,14 @@ def parse_args(argv=None):
                     help='weights from a checkpoint file in the reference\'s schema ({"model": state_dict, ...}, train_video_seg.py:159-177) '
                          'instead of the synthetic recipe (tools/synth.make_state_dict) -- e.g. the checkpoint scripts/bf16_trained_margins.py '
                          'trains on the GPU box with the HIP training step; the line says so in `data`')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: the rest of the clip (full_clip_fps, value_ci), '
+                         '--min-timed-s (sustained), HIP-event brackets on sampled frames of the timed window (roofline, memory_read), '
+                         'the CPU oracle baseline and the parity checks.  Without it --min-timed-s, --no-cpu-baseline, --cpu-frames, '
+                         '--sample-every and --apply-sample-every have no effect')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed step handed its caller to DIR/labels.npy (float32 '
+                         'label map) and DIR/bank_sizes.npy (float64 live bank entries per object); rank 0')
     ap.add_argument('--launch-check', action='store_true',
                     help='bring the N ranks up, run the mask all-gather on a dummy clip and print the line skeleton without '
                          'touching the GPU (tests/test_bench_launch.py: the launch logic on a CPU-only machine)')
@@ -275,14 +306,13 @@ def main(argv=None):
     s_first = 1 if stream_mode else pick_window(K, n_iter, golden_sizes)
     last_iter = max(n_iter, s_first + K - 1)        # K > 99: the timed region cycles through the clip's frames
 
+    from vfloodnet_amd import _lib as vlib
     timer = ConvTimer()
-    timed_launch = timer.install()
     # the memory read (bank scan + apply + finish) of the sampled frames, timed the same way
     mem_records = []                               # (bank entries summed over objects, HW, ev0, ev1)
     orig_memread = Engine._memory_read
 
     apply_records = []                             # the apply kernel of the same frames on its own: (entries, HW, ev0, ev1)
-    from vfloodnet_amd import _lib as vlib
     L_ = vlib.lib()
     orig_apply = L_.vfn_memread_apply
     cur_mem = {}
@@ -302,7 +332,6 @@ def main(argv=None):
         stored = bool(getattr(getattr(desc_ref, '_obj', None), 'scores', None))      # scores read back from the scan
         apply_records.append((cur_mem['entries'], cur_mem['HW'], e0, e1, stored))
         return rc
-    L_.vfn_memread_apply = timed_apply
 
     def timed_memread(self_, p_, fb_, update_bank_, kv_q_=None, out=None):
         if not timer.active:
@@ -313,7 +342,10 @@ def main(argv=None):
         orig_memread(self_, p_, fb_, update_bank_, kv_q_, out)
         e1.record()
         mem_records.append((sum(fb_._len_host), p_.HW, e0, e1))
-    Engine._memory_read = timed_memread
+    if args.full:                                    # (a plain run has no instrumented frames: the launches stay unwrapped)
+        timed_launch = timer.install()
+        L_.vfn_memread_apply = timed_apply
+        Engine._memory_read = timed_memread
     eng = model.engine()
     Hn, Wn = resized_hw(H0, W0, net_size)            # reference semantics: the network always sees the 480p frame
     eng.autotune(Hn, Wn, 2, only_missing=not args.autotune)      # the shipped tables cover C2 / C3 / C5 at reference semantics
@@ -322,7 +354,7 @@ def main(argv=None):
     if group_n:                                      # the batched lists exist before the tuner and the timers look at the plan
         plan.batch_set(group_n).dec_batch()
         eng.autotune(Hn, Wn, 2, only_missing=True)
-    for lst in plan.all_lists():
+    for lst in (plan.all_lists() if args.full else ()):
         for l in lst:
             if l.fn is timer.orig:
                 l.fn = timed_launch
@@ -377,7 +409,7 @@ def main(argv=None):
             # no prefetch into / out of a sampled frame: its kernels are timed alone on the device.  Otherwise the query
             # side looks up to three frames ahead (two frames per batched pass, ClipRunner._look_ahead)
             def is_sampled(u):
-                return s_first <= u <= s_first + K - 1 and ((u - s_first + 1) % args.sample_every == 0)
+                return args.full and s_first <= u <= s_first + K - 1 and ((u - s_first + 1) % args.sample_every == 0)
             timer.active = sampling and is_sampled(t)
             eng.eager = timer.active                 # (a sampled frame's launches are bracketed one by one: no graph replay)
             timer.light = (sampling and not timer.active and apply_every > 0 and s_first <= t <= s_first + K - 1
@@ -464,7 +496,7 @@ def main(argv=None):
     run_iters(1, s_first - 1, False)                                       # untimed pre-roll
     captures0 = sum(pl.graphs.captures for pl in eng.plans.values())
     t0 = bracket()
-    run_iters(s_first, s_first + K - 1, True)                              # ---- exactly K timed steps
+    run_iters(s_first, s_first + K - 1, args.full)                         # ---- exactly K timed steps
     captures_in_window = sum(pl.graphs.captures for pl in eng.plans.values()) - captures0
     gather_s = 0.0
     torch.cuda.synchronize()
@@ -474,18 +506,21 @@ def main(argv=None):
         torch.cuda.synchronize()
         gather_s = time.perf_counter() - g0
     t1 = bracket()
-    run_iters(s_first + K, last_iter, False)                               # rest of the clip, untimed
-    if dist_on:
-        vdist.gather_masks(labels[1:].unsqueeze(0), world, rank, world)
+    ran_to = s_first + K - 1                                               # last loop iteration run so far
+    if args.full:
+        run_iters(s_first + K, last_iter, False)                           # rest of the clip, untimed
+        if dist_on:
+            vdist.gather_masks(labels[1:].unsqueeze(0), world, rank, world)
+        ran_to = last_iter
     clip1 = bracket()
     # the int32 [T, obj_n] bank-size vector of every rank's clip travels beside the masks: one more, tiny
     # all-gather, outside every timed bracket
-    sizes_all = vdist.gather_bank_sizes([bank_sizes[:last_iter]], world, rank, world, dev)
+    sizes_all = vdist.gather_bank_sizes([bank_sizes[:ran_to]], world, rank, world, dev)
 
     # ---- sustained rate beyond the clip: the loop keeps cycling through the clip's frames with the bank at its budget
     # (every update evicts -- the regime a stream longer than 100 frames lives in); not part of `value`
     sustained = None
-    if args.min_timed_s > 0 and not stream_mode and (t1 - t0) < args.min_timed_s:
+    if args.full and args.min_timed_s > 0 and not stream_mode and (t1 - t0) < args.min_timed_s:
         n_extra = int(min(2000, max(K, (args.min_timed_s - (t1 - t0)) / max(1e-4, (t1 - t0) / K))))
         n_before = len(bank_sizes)
         run_iters(last_iter + 1, last_iter + n_extra, False)
@@ -505,7 +540,7 @@ def main(argv=None):
             dist.all_reduce(v, op=dist.ReduceOp.MAX)
         return float(v.item())
     elapsed = max_over_ranks(t1 - t0)
-    clip_elapsed = max_over_ranks(clip1 - clip0)
+    clip_elapsed = max_over_ranks(clip1 - clip0) if args.full else None
 
     def all_ranks(vals):
         """[world][len(vals)] on every rank: one small all-gather (outside every timed region)."""
@@ -526,6 +561,12 @@ def main(argv=None):
         if dist_on:
             dist.destroy_process_group()
         return 0
+
+    if args.dump_outputs:                            # what the loop handed its caller after the last timed step
+        import numpy as np
+        t_last = s_first + K - 1
+        dump_outputs(args.dump_outputs, {'labels': labels[t_last].float().cpu().numpy(),
+                                         'bank_sizes': np.asarray(bank_sizes[t_last - 1], dtype=np.float64)})
 
     # ---- roofline of the dominant kernel: the instrumented kernel with the most device time on the sampled frames
     # (every implicit-GEMM instantiation and the memory-read apply kernel; the others are listed in roofline.kernels)
@@ -608,14 +649,14 @@ def main(argv=None):
     # ---- whole-frame roofline: F_min(B) = 538.48 GFLOP + 3072*B*HW
     timed_sizes = bank_sizes[s_first - 1:s_first - 1 + K]
     b_mean = sum(sum(x) for x in timed_sizes) / (2.0 * K)
-    b_mean_clip = sum(sum(x) for x in bank_sizes[:n_iter]) / (2.0 * n_iter)
+    b_mean_clip = sum(sum(x) for x in bank_sizes[:n_iter]) / (2.0 * n_iter) if args.full else None
     fps = world * K / elapsed
-    full_clip_fps = world * last_iter / clip_elapsed
+    full_clip_fps = world * last_iter / clip_elapsed if args.full else None
     f_min = 538.48e9 + 3072.0 * b_mean * 1620
     frame_frac = (fps / world) * f_min / (peak * 1e12)
     f_ref = 666.56e9 + 3072.0 * b_mean * 1620          # op-for-op reference FLOPs (per-object duplicate convs counted)
     frame_frac_ref = (fps / world) * f_ref / (peak * 1e12)
-    f_min_clip = 538.48e9 + 3072.0 * b_mean_clip * 1620
+    f_min_clip = 538.48e9 + 3072.0 * b_mean_clip * 1620 if args.full else None
     # what the matrix pipe EXECUTES per frame: the plan's launch lists carry every launch's own FLOP (a Winograd-domain GEMM
     # 2 * 36 * tiles * Cin * Cout = 1/4 of the direct convolution it replaces); one memorize + one decoder pass + half a two-frame
     # query pass per frame, + the memory read / update contractions
@@ -633,7 +674,7 @@ def main(argv=None):
     # ---- CPU baseline + parity on the first frames of the same clip
     cpu = None
     parity = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import afb_urr_ref as O
         nthr = min(16, os.cpu_count() or 1)     # fastest setting measured on the GPU box's 256-core host (8/16/32/64/128 tried)
         torch.set_num_threads(nthr)
@@ -653,7 +694,7 @@ def main(argv=None):
                   'bank_sizes_equal': bank_sizes[:n_cpu] == ref['bank_sizes'],
                   'oracle_dtype': 'f32 (the reduced-precision modes are compared with the f32 oracle labels)'}
 
-    if world == 1 and golden is not None and seed == int(golden['seed']) and last_iter >= n_iter and not args.checkpoint:
+    if args.full and world == 1 and golden is not None and seed == int(golden['seed']) and last_iter >= n_iter and not args.checkpoint:
         import numpy as np
         refl = torch.from_numpy(np.unpackbits(golden['labels'], axis=-1)[..., :W0])
         lab = labels_raw[:n_frames].cpu()
@@ -668,7 +709,8 @@ def main(argv=None):
 
     timed_desc = (f'all {n_iter} loop iterations timed' if (s_first == 1 and K == n_iter) else
                   f'{K} iterations timed' + (f' (frames {s_first}-{s_first + K - 1}; frames 1-{s_first - 1} are an untimed pre-roll that '
-                                             f'builds the bank, the clip is finished untimed)' if not stream_mode and K < n_iter else ''))
+                                             f'builds the bank' + (', the clip is finished untimed)' if args.full else ')')
+                                             if not stream_mode and K < n_iter else ''))
     out = {'metric': 'segmented frames/sec at 480p' if args.workload == 'C2' else f'segmented frames/sec at {H0}p', 'value': round(fps, 3), 'unit': 'frames/s', 'n_gpus': world,
            'steps': K, 'warmup': Wm, 'ms_per_step': round(1e3 * elapsed / K, 3), 'higher_is_better': True,
            'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPES[args.precision],
@@ -682,7 +724,7 @@ def main(argv=None):
                       'grouped_frames': group_n or None,
                       'timed_frames': [s_first, s_first + K - 1], 'preroll_frames': s_first - 1, 'warm_steps_run': warm_steps,
                       'mean_bank_entries_per_object': round(b_mean, 1),
-                      'full_clip_mean_bank_entries_per_object': round(b_mean_clip, 1),
+                      'full_clip_mean_bank_entries_per_object': round(b_mean_clip, 1) if args.full else None,
                       'network_resolution': f'{Hn}x{Wn} ' + ('(native)' if args.native and (Hn, Wn) == (H0, W0) else '(reference semantics: 480-pixel short edge)'),
                       'frame_mfma_frac_Fmin': round(frame_frac, 4) if mem_every == 1 else None,
                       'frame_mfma_frac_executed': round(frame_frac_exec, 4) if mem_every == 1 else None,
@@ -695,7 +737,7 @@ def main(argv=None):
                       # queue run in order): [found, candidates tried] per probe of this process (vfloodnet_amd._lib.independent_stream)
                       'side_stream_probes': [[bool(a_), int(b_)] for a_, b_ in vlib.PROBES],
                       'frame_mfma_frac_Fref_reference_equivalent': round(frame_frac_ref, 4) if mem_every == 1 else None},
-           'full_clip_fps': round(full_clip_fps, 3),
+           'full_clip_fps': round(full_clip_fps, 3) if args.full else None,
            # `value` is K frames (0.12 s at the driver's --steps 20): a 1-2 % effect cannot be read off it.  The same run's other clocks
            # on the same kernels: every iteration of the clip (pre-roll + window + rest; includes the instrumented frames, so it is a
            # lower bound) and the median host wall between consecutive step completions inside the window
@@ -703,8 +745,8 @@ def main(argv=None):
                         'p50_frame_fps': round(world * 1e3 / tms[len(tms) // 2], 3),
                         'low': round(min(fps, full_clip_fps), 3), 'high': round(max(fps, full_clip_fps, world * 1e3 / tms[len(tms) // 2]), 3),
                         'graph_captures_in_window': int(captures_in_window),
-                        'note': 'quote A/Bs below 2 % from full_clip_fps (99 steps) of alternating runs on one box, not from `value`'},
-           'full_clip_frame_mfma_frac_Fmin': round((full_clip_fps / world) * f_min_clip / (peak * 1e12), 4) if mem_every == 1 else None,
+                        'note': 'quote A/Bs below 2 % from full_clip_fps (99 steps) of alternating runs on one box, not from `value`'} if args.full else None,
+           'full_clip_frame_mfma_frac_Fmin': round((full_clip_fps / world) * f_min_clip / (peak * 1e12), 4) if mem_every == 1 and args.full else None,
            'frame_ms': frame_stats, 'sustained': sustained,
            'roofline': roof, 'memory_read': memread, 'cpu_baseline': cpu, 'parity': parity}
     # ---- what a multi-GPU record needs to show that N ranks met over RCCL, and where the time went
@@ -715,7 +757,7 @@ def main(argv=None):
         'all_gather_ms_per_rank': [round(1e3 * r_[1], 3) for r_ in per_rank] if dist_on else None,
         'all_gather_bytes_per_rank': int(K * H0 * W0) if dist_on else None,
         'bank_sizes_gathered': {'clips': len(sizes_all), 'shape_per_clip': [int(v) for v in sizes_all[0].shape], 'dtype': 'int32',
-                                'own_block_intact': bool(torch.equal(sizes_all[0], torch.tensor(bank_sizes[:last_iter], dtype=torch.int32))),
+                                'own_block_intact': bool(torch.equal(sizes_all[0], torch.tensor(bank_sizes[:ran_to], dtype=torch.int32))),
                                 'note': 'int32 [T, obj_n] live bank entries per frame of every rank\'s clip, gathered beside the masks outside the timed bracket (dist.gather_bank_sizes)'},
         'frames_per_s_per_rank': [round(x, 3) for x in rates],
         'frames_per_s_per_rank_min': round(min(rates), 3), 'frames_per_s_per_rank_max': round(max(rates), 3),

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 O=gpurun_out
-B="python3 bench.py"
+B="python3 bench.py --full"
 timeout 300 $B --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_driver_cmd.json 2> $O/driver.err
 timeout 300 $B --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_driver_cmd_2.json 2>> $O/driver.err
 timeout 400 $B > $O/r06_bench_default.json 2> $O/default.err

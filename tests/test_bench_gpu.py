@@ -1,5 +1,5 @@
-"""bench.py end to end on the GPU box: the driver's command line, the self-launched N > 1 path (two ranks sharing the
-one device over gloo), and the C3 / C5 lines with their parity object."""
+"""bench.py end to end on the GPU box: the driver's command line (plain, with --dump-outputs, and --full), the self-launched
+N > 1 path (two ranks sharing the one device over gloo), and the C3 / C5 lines with their parity object."""
 import json
 import os
 import subprocess
@@ -23,7 +23,7 @@ def _run(args, extra_env=None, timeout=900):
 
 
 def test_driver_command_is_the_c2_clip(gpu):
-    d = _run(['--gpus', '1', '--steps', '20', '--warmup', '5', '--cpu-frames', '3'])
+    d = _run(['--gpus', '1', '--steps', '20', '--warmup', '5', '--cpu-frames', '3', '--full'])
     assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['unit'] == 'frames/s' and d['dtype'] == 'f32'
     assert d['config']['workload'].startswith('C2: 100-frame 480x854')
     # the 20 timed frames carry the full clip's mean bank (within 3 %) and the whole clip was run
@@ -35,6 +35,30 @@ def test_driver_command_is_the_c2_clip(gpu):
     r = d['roofline']
     assert r['bound'] == 'mfma' and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-3 and 0.2 < r['frac'] < 1.0
     assert d['cpu_baseline']['kind'] == 'port' and d['cpu_baseline']['value'] > 0
+
+
+def test_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain run (no --full) is set-up, warm-up, the timed steps and the line: the fields --full adds are null.  --dump-outputs
+    writes the last timed step's label map and bank sizes, which match the reference's own run of the same clip at that frame."""
+    import numpy as np
+    from oracle import afb_urr_ref as O
+    d = _run(['--gpus', '1', '--steps', '20', '--warmup', '5', '--dump-outputs', str(tmp_path)])
+    assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['unit'] == 'frames/s' and d['dtype'] == 'f32'
+    assert d['metric'] == 'segmented frames/sec at 480p' and d['higher_is_better'] is True
+    assert abs(d['ms_per_step'] * d['value'] / 1e3 - 1) < 1e-3
+    for k in ('full_clip_fps', 'value_ci', 'sustained', 'roofline', 'memory_read', 'cpu_baseline', 'parity'):
+        assert d[k] is None, k
+    t_first, t_last = d['config']['timed_frames']
+    assert t_last - t_first + 1 == 20
+    lab, sizes = np.load(tmp_path / 'labels.npy'), np.load(tmp_path / 'bank_sizes.npy')
+    assert lab.dtype == np.float32 and lab.shape == (480, 854) and set(np.unique(lab).tolist()) <= {0.0, 1.0}
+    assert sizes.dtype == np.float64 and sizes.shape == (2,)
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'c2_480x854_100.npz'))
+    assert np.abs(sizes - g['bank_sizes'][t_last - 1]).max() <= max(8, 0.001 * sizes.max())
+    ref = O.postprocessing_pred(np.unpackbits(g['labels'][t_last], axis=-1)[:, :854])
+    inter = [((lab == c) & (ref == c)).sum() for c in (0, 1)]
+    union = [((lab == c) | (ref == c)).sum() for c in (0, 1)]
+    assert sum(i / u for i, u in zip(inter, union)) / 2 >= 0.99
 
 
 def test_self_launch_two_ranks_on_one_device(gpu):
@@ -54,7 +78,7 @@ def test_self_launch_two_ranks_on_one_device(gpu):
 @pytest.mark.parametrize('workload,steps', [('C3', 12), ('C5', 12)])
 def test_reduced_precision_lines_carry_parity(gpu, workload, steps):
     d = _run(['--workload', workload, '--precision', 'bf16x3', '--steps', str(steps), '--warmup', '1', '--min-warm-s', '0',
-              '--cpu-frames', '5'])
+              '--cpu-frames', '5', '--full'])
     assert d['dtype'].startswith('bf16x3') and d['parity'] is not None
     assert d['parity']['miou_vs_oracle'] >= 0.99 and d['parity']['bank_sizes_equal']
     assert d['config']['network_resolution'].startswith('480x853')

@@ -61,3 +61,20 @@ def test_window_selection():
     full = sum(sum(x) for x in sizes) / 99
     win = sum(sum(x) for x in sizes[s - 1:s + 19]) / 20
     assert abs(win - full) / full < 0.01, (s, win, full)
+
+
+def test_plain_by_default_and_dump_outputs(tmp_path):
+    """Everything beyond the headline waits for --full; --dump-outputs writes float .npy files within the 64 MB cap."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    a = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    a = bench.parse_args(['--full', '--dump-outputs', str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    lab = (np.arange(480 * 854) % 2).reshape(480, 854).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / 'out'), {'labels': lab, 'bank_sizes': np.array([3240.0, 3240.0])})
+    assert np.array_equal(np.load(tmp_path / 'out' / 'labels.npy'), lab)
+    assert np.load(tmp_path / 'out' / 'bank_sizes.npy').dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros((64 << 20) // 4 + 1, np.float32)})

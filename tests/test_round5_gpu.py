@@ -128,7 +128,7 @@ def test_bench_line_through_the_rccl_branch_and_with_five_apply_samples(gpu):
     (its time and byte count are reported), and the dominant kernel's roofline rests on >= 3 bracketed launches with the driver's
     --steps 20 (one fully sampled frame + the apply kernel alone on every 5th frame)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '2', '--min-warm-s', '0',
-                        '--min-timed-s', '0', '--no-cpu-baseline'], env=_child_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        '--min-timed-s', '0', '--no-cpu-baseline', '--full'], env=_child_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
