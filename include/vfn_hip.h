@@ -27,9 +27,9 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 12
+#define VFN_ABI_VERSION 13
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
-       VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8 };
+       VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9 };
 int vfn_abi_version(void);
 int vfn_sizeof_desc(int which);
 
@@ -500,6 +500,33 @@ int vfn_bank_scan(const vfn_bankscan_desc* d, void* stream);
 int vfn_bank_scan_finish(const float* part, int nsplit, int HW, int obj_n, int mode, float* ml, int* idx,
                          float* corr, const float* colscale, void* stream);
 int vfn_memread_apply(const vfn_memread_desc* d, void* stream);
+
+/* Certified bank match (ABI 13): the f32 match of vfn_bank_scan (mode 1, precision 0) + vfn_bank_scan_finish, bit for bit, from
+ * bf16x3 scores.  Per column: bf16x3 best / runner-up over the bank (keys from the split image), certification by a derived
+ * error bound (csrc/memory_read.hip, above bank_match_certify_kernel), the winner rescored with the f32 kernel's own MFMA
+ * sequence; columns that cannot be certified are listed on the device and scanned in f32.  No host synchronisation. */
+typedef struct vfn_bankmatch_desc {
+    const float* q;           /* new keys [obj][HW][ldq], stride_q floats per object */
+    const float* bank_k;      /* [obj][cap][128] */
+    const void* bank_k_lp;    /* [obj][cap][128 hi | 128 lo] bf16 key image (vfn_bank_refresh_lp / vfn_bank_refresh_lp_keys), required */
+    const int* bank_len;      /* [obj], device */
+    const float* rowscale;    /* [obj][stride_rs] 1/max(||key||, 1e-12) */
+    const float* qnorm;       /* [obj][HW] ||q|| (vfn_row_norms) */
+    const float* colscale;    /* [obj][HW] 1/max(||q||, 1e-12) */
+    float* part_x3;           /* [obj][nsplit][HW][4] scratch */
+    float* part_f32;          /* [obj][nsplit_fb][HW][2] scratch */
+    int* ulist;               /* [obj][HW] scratch: the uncertain columns */
+    int* ucount;              /* [obj]: uncertain columns of this call (zeroed by the launcher on the stream) */
+    int* utotal;              /* [obj] or NULL: running count of uncertain columns (incremented, never reset here) */
+    int* work_counter;        /* one int of device memory (queue head of the persistent scans) */
+    int* match_idx;           /* [obj][HW] out: as vfn_bank_scan_finish mode 1 */
+    float* match_corr;        /* [obj][HW] out */
+    long long stride_q, stride_k, stride_rs;
+    int ldq, HW, obj_n;
+    int nsplit;               /* bank slices of the bf16x3 scan */
+    int nsplit_fb;            /* bank slices of the f32 scan over the listed columns */
+} vfn_bankmatch_desc;
+int vfn_bank_match_certified(const vfn_bankmatch_desc* d, void* stream);
 int vfn_memread_finish(const vfn_memread_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ feature-bank maintenance
@@ -552,6 +579,8 @@ typedef struct vfn_bank_desc {
  * all_rows = 0: after vfn_bank_merge + vfn_bank_append of the same descriptor, re-split only the entries that update
  * changed (merged or appended; every entry when it compacted the bank).  all_rows = 1: every live entry. */
 int vfn_bank_refresh_lp(const vfn_bank_desc* d, void* bank_k_lp, void* bank_v_lp, int all_rows, void* stream);
+/* The key half of vfn_bank_refresh_lp alone (the f32 match keeps no value image). */
+int vfn_bank_refresh_lp_keys(const vfn_bank_desc* d, void* bank_k_lp, int all_rows, void* stream);
 
 int vfn_row_norms(const float* x, long long stride_obj, int ld, int dim, const int* len_dev, int rows,
                   int obj_n, float* nrm, float* inv /* 1/max(nrm,1e-12) or NULL */, long long stride_n, void* stream);

@@ -78,6 +78,14 @@ class MemReadDesc(C.Structure):
                 ('nsplit', C.c_int), ('precision', C.c_int), ('bank_k_lp', c_fp), ('bank_v_lp', c_fp), ('scores', c_fp), ('stride_scores', C.c_longlong)]
 
 
+class BankMatchDesc(C.Structure):
+    _fields_ = [('q', c_fp), ('bank_k', c_fp), ('bank_k_lp', c_fp), ('bank_len', c_fp), ('rowscale', c_fp), ('qnorm', c_fp),
+                ('colscale', c_fp), ('part_x3', c_fp), ('part_f32', c_fp), ('ulist', c_fp), ('ucount', c_fp), ('utotal', c_fp),
+                ('work_counter', c_fp), ('match_idx', c_fp), ('match_corr', c_fp),
+                ('stride_q', C.c_longlong), ('stride_k', C.c_longlong), ('stride_rs', C.c_longlong),
+                ('ldq', C.c_int), ('HW', C.c_int), ('obj_n', C.c_int), ('nsplit', C.c_int), ('nsplit_fb', C.c_int)]
+
+
 class BankDesc(C.Structure):
     _fields_ = [('bank_k', c_fp), ('bank_v', c_fp), ('info', c_fp),
                 ('scratch_k', c_fp), ('scratch_v', c_fp), ('scratch_info', c_fp),
@@ -92,8 +100,8 @@ class BankDesc(C.Structure):
                 ('obj_n', C.c_int), ('cap', C.c_int), ('rm_class', C.c_int), ('rm_request', C.c_int)]
 
 
-ABI_VERSION = 12         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
-DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry}     # vfn_sizeof_desc(which)
+ABI_VERSION = 13         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
+DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc}     # vfn_sizeof_desc(which)
 
 
 def lib():
@@ -147,6 +155,8 @@ def _declare(L):
     L.vfn_bank_refresh_norms.argtypes = [C.POINTER(BankDesc), p, p, p, p]
     L.vfn_conv_wgrad_f32.argtypes = [C.POINTER(WgradDesc), p]
     L.vfn_bank_refresh_lp.argtypes = [C.POINTER(BankDesc), p, p, i, p]
+    L.vfn_bank_refresh_lp_keys.argtypes = [C.POINTER(BankDesc), p, i, p]
+    L.vfn_bank_match_certified.argtypes = [C.POINTER(BankMatchDesc), p]
     L.vfn_stem_wgrad_scratch_floats.argtypes = [i]
     L.vfn_stem_wgrad_scratch_floats.restype = i
     for name, args in SIGNATURES.items():
@@ -232,6 +242,7 @@ ALL_SYMBOLS = sorted(list(SIGNATURES) + [
     'vfn_abi_version', 'vfn_sizeof_desc', 'vfn_conv_cfg_count', 'vfn_conv_cfg_tile', 'vfn_conv_cfg_info', 'vfn_conv_cfg_wk', 'vfn_conv_cfg_tpb', 'vfn_conv_cfg_kind', 'vfn_conv_cfg_name', 'vfn_conv2d_nhwc_f32', 'vfn_conv2d_nhwc_bf16', 'vfn_conv2d_nhwc_bf16x3',
     'vfn_stem_conv7x7_f32',
     'vfn_bank_scan', 'vfn_memread_apply', 'vfn_memread_finish', 'vfn_bank_merge', 'vfn_bank_append', 'vfn_bank_remove', 'vfn_bank_refresh_norms', 'vfn_bank_refresh_lp', 'vfn_conv_wgrad_f32',
+    'vfn_bank_refresh_lp_keys', 'vfn_bank_match_certified',
     'vfn_stem_wgrad_scratch_floats'])
 
 

@@ -3,6 +3,7 @@
 // 2: vfn_conv_desc.w_packed, vfn_bankscan_desc.precision, vfn_memread_desc.precision; bf16 / bf16x3 and I/O entry points
 // 3: vfn_memread_desc.wide (added at 2 without a bump), vfn_conv_cfg_info, vfn_sizeof_desc
 // 4: PNG / JPEG / segment-uncertainty / norm-refresh entry points (round 2)
+// 13: vfn_bankmatch_desc, vfn_bank_match_certified, vfn_bank_refresh_lp_keys
 extern "C" int vfn_abi_version(void) { return VFN_ABI_VERSION; }
 
 // sizeof of every descriptor as THIS library was compiled: a binding whose struct layout drifted fails its
@@ -18,6 +19,7 @@ extern "C" int vfn_sizeof_desc(int which) {
         case VFN_DESC_REFRESH_FILTER: return (int)sizeof(vfn_refresh_filter);
         case VFN_DESC_REFRESH_EPILOGUE: return (int)sizeof(vfn_refresh_epilogue);
         case VFN_DESC_GATHER: return (int)sizeof(vfn_gather_entry);
+        case VFN_DESC_BANKMATCH: return (int)sizeof(vfn_bankmatch_desc);
     }
     return -1;
 }

@@ -407,6 +407,7 @@ __global__ void bank_refresh_lp_kernel(const vfn_bank_desc p, char* __restrict__
 #pragma unroll
             for (int r = 0; r < 8; ++r)
                 if (blk * 8 + r < newlen) split_key_row(blk * 8 + r);
+            if (!vlp) continue;                                   // keys only (vfn_bank_refresh_lp_keys)
             char* dst = VL + (size_t)blk * (8 * DV * 4);
             for (int c = lane; c < DV; c += 64) {
                 bf16x8_t h, l;
@@ -427,6 +428,7 @@ __global__ void bank_refresh_lp_kernel(const vfn_bank_desc p, char* __restrict__
         const int row = (corr[it] > p.thres_close) ? idx[it] : base + pos[it];
         if (row < 0 || row >= newlen) continue;
         split_key_row(row);
+        if (!vlp) continue;
         char* dst = VL + (size_t)(row >> 3) * (8 * DV * 4) + (row & 7) * 2;
         for (int c = lane; c < DV; c += 64) {                     // one row of a block: 2-byte stores, 16 bytes apart
             const float x = V[(size_t)row * DV + c];
@@ -553,6 +555,14 @@ extern "C" int vfn_bank_refresh_norms(const vfn_bank_desc* d, float* bank_knorm,
     if (!bank_knorm || !bank_kinv || !bank_vnorm) return VFN_ERR_ARG;
     hipLaunchKernelGGL(bank_refresh_norms_kernel, dim3(1024, d->obj_n), dim3(256), 0, (hipStream_t)stream, *d,
                        bank_knorm, bank_kinv, bank_vnorm);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_bank_refresh_lp_keys(const vfn_bank_desc* d, void* bank_k_lp, int all_rows, void* stream) {
+    if (!bank_desc_ok(d) || !bank_k_lp) return VFN_ERR_ARG;
+    if (!all_rows && (!d->plan || !d->stats || !d->match_idx || !d->match_corr || !d->app_pos)) return VFN_ERR_ARG;
+    hipLaunchKernelGGL(bank_refresh_lp_kernel, dim3(all_rows ? 4096 : 1024, d->obj_n), dim3(256), 0, (hipStream_t)stream, *d,
+                       (char*)bank_k_lp, (char*)nullptr, all_rows);
     return vfn_check_launch();
 }
 

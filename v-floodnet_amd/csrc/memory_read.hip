@@ -193,9 +193,14 @@ constexpr int QTS = 128;    // query columns per scan workgroup
 __device__ unsigned long long vfn_census_buf[4096 * 4];
 #endif
 
-template <int MODE, int PREC = 0>
+// GATHER (MODE 1, f32): the query columns of an object are those listed in gather.list[obj][0 .. count[obj]) (the columns the
+// certified match could not settle, vfn_bank_match_certified); part is written at the LIST position.  Same products in the same
+// order per (entry, column) as the full scan.
+struct scan_gather { const int* list; const int* count; };
+
+template <int MODE, int PREC = 0, bool GATHER = false>
 __global__ __launch_bounds__(256, 2)
-void bank_scan_kernel(const vfn_bankscan_desc p) {
+void bank_scan_kernel(const vfn_bankscan_desc p, const scan_gather gather) {
 #ifdef VFN_CENSUS
     const unsigned long long census_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -212,17 +217,35 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
     // third of the kernel ran half-empty.  With ~2000 small items every slot stays paired until the queue is dry.
     // An item's result depends only on the item, so the output is bit-identical whichever workgroup computes it.
     const int qtiles = (p.HW + QTS - 1) / QTS;
-    const int total = p.nsplit * qtiles * p.obj_n;
+    int total = p.nsplit * qtiles * p.obj_n;
+    if constexpr (GATHER) {                            // per object: nsplit x ceil(count / 128) items, object by object
+        total = 0;
+        for (int o = 0; o < p.obj_n; ++o) total += p.nsplit * ((gather.count[o] + QTS - 1) / QTS);
+    }
   for (;;) {
     if (tid == 0) s_item = atomicAdd(p.work_counter, 1);
     __syncthreads();
-    const int item = s_item;
+    int item = s_item;
     __syncthreads();                                   // (everyone has the item before thread 0 draws the next one)
     if (item >= total) break;
-    const int obj = item % p.obj_n;
-    const int qt = (item / p.obj_n) % qtiles;
-    const int split = item / (p.obj_n * qtiles);
-    const int q0 = qt * QTS + wave * 32;             // first query of this wave
+    int obj, qt, split;
+    if constexpr (GATHER) {
+        obj = 0;
+        for (;;) {
+            const int n = p.nsplit * ((gather.count[obj] + QTS - 1) / QTS);
+            if (item < n) break;
+            item -= n; ++obj;
+        }
+        const int qtl = (gather.count[obj] + QTS - 1) / QTS;
+        qt = item % qtl;
+        split = item / qtl;
+    } else {
+        obj = item % p.obj_n;
+        qt = (item / p.obj_n) % qtiles;
+        split = item / (p.obj_n * qtiles);
+    }
+    const int q0 = qt * QTS + wave * 32;             // first query of this wave (GATHER: first list position)
+    const int ncol = GATHER ? gather.count[obj] : p.HW;
     const int B = p.bank_len[obj];
     // reduced precision with a kept split-bf16 image of the keys (vfn_bank_refresh_lp): same bytes per row as f32, the
     // chunk lands in LDS as the operand image itself (hi | lo halves, chunks swizzled like swzk)
@@ -238,7 +261,8 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
     f32x4 qf[PREC == 0 ? 16 : 1];
     bf16x8 qh[PREC == 0 ? 1 : 8], ql[PREC == 2 ? 8 : 1];
     {
-        const int q = min(q0 + li, p.HW - 1);                    // columns past HW are never written out
+        int q = min(q0 + li, ncol - 1);                          // columns past HW are never written out
+        if constexpr (GATHER) q = gather.list[(size_t)obj * p.HW + q];
         if constexpr (PREC == 0) {
             const float* qrow = Q + (size_t)q * p.ldq + 4 * lh;
 #pragma unroll
@@ -257,6 +281,8 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
 
     float run_m = -INFINITY, run_l = 0.f;
     int run_i = 0x7fffffff;
+    float run_2 = -INFINITY;                           // MODE 2: runner-up score
+    bool sick = false;                                 // MODE 2: a live entry of the slice has a zero / non-finite norm
     __syncthreads();                                   // chunk c_lo landed (the barrier drains the LDS-DMA)
 
     for (int c = c_lo; c < c_hi; ++c) {
@@ -269,13 +295,15 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
         // MODE 1: the chunk's 32 row scales per lane (1 / |key|), requested BEFORE the score MFMAs (round 5: they were loaded behind
         // them, inside a range test per group, and used at once -- one exposed L2 round trip at the end of every chunk).  Rows past the
         // bank's end lie inside the slab (finite scratch) and are ignored by the comparison below.
-        f32x4 scv[MODE == 1 ? 2 : 1][MODE == 1 ? 4 : 1];
-        if constexpr (MODE == 1) {
+        f32x4 scv[MODE >= 1 ? 2 : 1][MODE >= 1 ? 4 : 1];
+        float rs_lane = 1.f;
+        if constexpr (MODE >= 1) {
             const float* rs = p.rowscale + (size_t)obj * p.stride_rs;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) scv[i][g] = *reinterpret_cast<const f32x4*>(rs + b0 + 32 * i + 4 * lh + 8 * g);
+            if constexpr (MODE == 2) rs_lane = rs[b0 + lane];     // entry b0 + lane: health check below
         }
         f32x16 acc[2];
 #pragma unroll
@@ -391,16 +419,20 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {            // registers 4g..4g+3 = rows +8g .. +3: one 16-byte load
                     const int row0 = b0 + 32 * i + 4 * lh + 8 * g;
-                    const f32x4 sc = scv[MODE == 1 ? i : 0][MODE == 1 ? g : 0];
+                    const f32x4 sc = scv[MODE >= 1 ? i : 0][MODE >= 1 ? g : 0];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int row = row0 + j;
                         if (row < B) {
                             const float s_ = acc[i][4 * g + j] * sc[j];
+                            // MODE 2: runner-up = median(s, best, runner-up) before the best moves (best >= runner-up)
+                            if constexpr (MODE == 2) run_2 = __builtin_amdgcn_fmed3f(s_, run_m, run_2);
                             if (s_ > run_m) { run_m = s_; run_i = row; }   // (ties: smaller row wins, below)
                         }
                     }
                 }
+            // rowscale = 1 / max(||key||, 1e-12): zero, tiny, NaN (fmaxf drops it: 1e12) and infinite (0) norms all fall outside
+            if constexpr (MODE == 2) sick |= (b0 + lane < B) && !(rs_lane > 0.f && rs_lane < 1e12f);
         }
         __syncthreads();                               // next chunk landed; this buffer is free again
     }
@@ -416,8 +448,16 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
             run_m = mn; run_l = l;
         } else {
             const int oi = __shfl_xor(run_i, 32, 64);
+            if constexpr (MODE == 2) {
+                const float o2 = __shfl_xor(run_2, 32, 64);
+                if (om > run_m || (om == run_m && oi < run_i)) run_2 = fmaxf(run_m, o2);
+                else run_2 = fmaxf(run_2, om);
+            }
             if (om > run_m || (om == run_m && oi < run_i)) { run_m = om; run_i = oi; }
         }
+    }
+    if constexpr (MODE == 2) {
+        if (__ballot(sick) != 0) run_2 = INFINITY;    // (every wave of the workgroup saw the same entries)
     }
 #ifdef VFN_CENSUS
     if (threadIdx.x == 0) {
@@ -432,10 +472,15 @@ void bank_scan_kernel(const vfn_bankscan_desc p) {
     }
 #endif
     const int q = q0 + li;
-    if (lh == 0 && q < p.HW) {
-        float* dst = p.part + (((size_t)obj * p.nsplit + split) * p.HW + q) * 2;
-        dst[0] = run_m;
-        dst[1] = (MODE == 0) ? run_l : __int_as_float(run_i);
+    if (lh == 0 && q < ncol) {
+        if constexpr (MODE == 2) {
+            float* dst = p.part + (((size_t)obj * p.nsplit + split) * p.HW + q) * 4;
+            *reinterpret_cast<f32x4*>(dst) = f32x4{run_m, __int_as_float(run_i), run_2, 0.f};
+        } else {
+            float* dst = p.part + (((size_t)obj * p.nsplit + split) * p.HW + q) * 2;
+            dst[0] = run_m;
+            dst[1] = (MODE == 0) ? run_l : __int_as_float(run_i);
+        }
     }
   }
 }
@@ -674,6 +719,132 @@ __global__ void bank_scan_finish_kernel(const float* __restrict__ part, int nspl
     if (j != 0 || !live) return;
     if (MODE == 0) { ml[(size_t)i * 2] = m; ml[(size_t)i * 2 + 1] = x; }
     else { idx[i] = __float_as_int(x); corr[i] = m * colscale[i]; }
+}
+
+// ------------------------------------------------------------------ certified bank match (f32 mode of FeatureBank.update)
+// The update needs, per new key q, only the arg-max entry b* of  f(b) = fl(F(b) * rowscale[b])  (F = the f32 MFMA dot of
+// bank_scan_kernel<1, 0>) and f(b*).  vfn_bank_match_certified gets both bit for bit at a fraction of the f32 matrix work:
+//   1. bank_scan_kernel<2, 2>: a(b) = fl(A(b) * rowscale[b]) with A the bf16x3 dot (keys from the split image, q split in
+//      registers); per (slice, column) the best a, its entry and the runner-up a (+inf when a live entry of the slice has a
+//      zero or non-finite norm).
+//   2. bank_match_certify_kernel: fold the slices; a column is CERTIFIED when  best - runner-up > margin(q).  Its winner's
+//      f(b*) is recomputed with the f32 kernel's instruction sequence (one 32x32 tile, diagonal = 32 (entry, column) pairs) and
+//      written with its index; any other column goes on a device list.
+//   3. bank_scan_kernel<1, 0, GATHER> over the listed columns + bank_scan_finish_kernel<1, GATHER>: the f32 path itself.
+//
+// The bound.  Per column, with k = the 128 key channels, K = key, Q = q, |.| = 2-norm, u = 2^-23 (one f32 ulp: no rounding
+// mode of the matrix cores is assumed beyond "each addition or product errs by at most u times the sum of the magnitudes it
+// combines", which covers round-to-nearest, truncation and wide internal sums):
+//   split   x = hi + lo + e,  hi = RNE_bf16(x), lo = RNE_bf16(x - hi) (x - hi is exact in f32): |lo| <= 2^-8 (1 + 2^-8) |x|,
+//           |e| <= 2^-16 |x|.  The bf16x3 terms hiK hiQ + hiK loQ + loK hiQ miss  loK loQ + eK Q + (hiK + loK) eQ  per k:
+//           <= (2^-16 (1 + 2^-7) + 2^-16 + 2^-16 (1 + 2^-16)) |K_k Q_k| <= 3.01 * 2^-16 |K_k Q_k|.
+//   sums    bf16 x bf16 products are exact in f32; the 384 terms (sum of magnitudes <= 1.02 sum|K_k Q_k|) take <= 384
+//           roundings: <= 384 u * 1.02 sum|K_k Q_k|.  The f32 kernel: 128 products and 128 additions, <= 256 u * sum|K_k Q_k|
+//           from the exact dot.  Cauchy-Schwarz: sum|K_k Q_k| <= |K| |Q|.
+//   so      |A - F| <= (3.01 * 2^-16 + 648 u) |K| |Q| = (4.593e-5 + 7.725e-5) |K| |Q| <= 1.232e-4 |K| |Q|.
+//   scaling a and f are A and F times the same s = rowscale[b], each rounded once: |a - f| <= |A - F| s + u (|A| + |F|) s, and
+//           |K| s <= 1 + 2^-16 (s = 1/|K| as vfn_row_norms computes it; smaller for |K| < 1e-12), |A|, |F| <= 1.03 |K| |Q|:
+//           |a - f| <= (1.232e-4 + 2.5e-7) (1 + 2^-16) |Q| <= 1.24e-4 |Q|.
+//   flushed subnormal operands or products add at most 3 * 128 * 2^-126 max|Q_k| per dot, times s <= 1e12: < 2^-77 |Q|.
+//   |Q| is taken as qnorm * (1 + 2^-16) (the f32 norm of vfn_row_norms), so  E(q) = 1.25e-4 * qnorm + 2^-64  bounds |a - f|
+//   for every entry of the column.
+// Certification: if  a(b1) - a(b) > 2 E  for every b != b1, then  f(b1) >= a(b1) - E > a(b) + E >= f(b): b1 is the strict f32
+// arg-max, so no tie rule is involved and f(b1) is the value the f32 path keeps.  The margin used is twice that, 4 E(q) (about
+// 5e-4 in cosine units).  A column is never certified when qnorm is 0, above 2^60 (products could overflow) or not finite, when
+// its best score is not finite, or when some live entry's norm is zero / non-finite (runner-up = +inf); equal best scores give a
+// zero gap.  Every such column takes the f32 path.
+constexpr float MATCH_EPS_REL = 1.25e-4f;
+constexpr float MATCH_EPS_ABS = 5.421010862427522e-20f;    // 2^-64
+constexpr float MATCH_QNORM_MAX = 1.152921504606846976e18f;  // 2^60
+
+// One wave = 32 columns of one object: fold the bf16x3 slice partials (lane half lh takes the slices lh, lh + 2, ..., then the
+// halves meet), certify, and for certified columns form f(b1) as bank_scan_kernel<1, 0> forms it: A row li = key b1 of column
+// li, B column li = that column's query, k = 8kk + 4lh + t, 64 v_mfma_f32_32x32x2f32 from a zero accumulator; element (li, li)
+// is then multiplied by rowscale[b1] and by colscale[q] as bank_scan_finish_kernel<1> does.  An MFMA output element depends only
+// on its own A row and B column, so the diagonal is what the f32 scan computes for that (entry, column) pair.
+__global__ __launch_bounds__(64)
+void bank_match_certify_kernel(const vfn_bankmatch_desc p) {
+    const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
+    const int obj = blockIdx.y, q0 = blockIdx.x * 32;
+    const int q = q0 + li, qc = min(q, p.HW - 1);
+    float m = -INFINITY, m2 = -INFINITY;
+    int bi = 0x7fffffff;
+    auto fold = [&](float om, int oi, float o2) {          // runner-up = the largest of the other three (+inf stays +inf)
+        if (om > m || (om == m && oi < bi)) { m2 = fmaxf(fmaxf(m, m2), o2); m = om; bi = oi; }
+        else m2 = fmaxf(fmaxf(m2, om), o2);
+    };
+    const float* part = p.part_x3 + ((size_t)obj * p.nsplit * p.HW + qc) * 4;
+#pragma unroll 4
+    for (int s = lh; s < p.nsplit; s += 2) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(part + (size_t)s * p.HW * 4);
+        fold(v[0], __float_as_int(v[1]), v[2]);
+    }
+    fold(__shfl_xor(m, 32, 64), __shfl_xor(bi, 32, 64), __shfl_xor(m2, 32, 64));
+
+    const size_t col = (size_t)obj * p.HW + qc;
+    const float qn = p.qnorm[col];
+    const float margin = 4.f * (MATCH_EPS_REL * qn + MATCH_EPS_ABS);
+    const bool cert = q < p.HW && qn > 0.f && qn <= MATCH_QNORM_MAX && m > -INFINITY && m < INFINITY && (m - m2) > margin;
+
+    // rescore (every lane takes part in the MFMAs; uncertain columns multiply zeros)
+    const float* krow = p.bank_k + (size_t)obj * p.stride_k + (size_t)(cert ? bi : 0) * DK + 4 * lh;
+    const float* qrow = p.q + (size_t)obj * p.stride_q + (size_t)qc * p.ldq + 4 * lh;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+        f32x4 a = *reinterpret_cast<const f32x4*>(krow + 8 * kk);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(qrow + 8 * kk);
+        if (!cert) a = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
+    }
+    // element (row li, column li) sits in lane li + 32 * ((li >> 2) & 1), register (li & 3) + 4 * (li >> 3)
+    const int rsel = (li & 3) + 4 * (li >> 3);
+    float dot = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dot = (r == rsel) ? acc[r] : dot;
+    if (lh != ((li >> 2) & 1)) return;
+    if (cert) {
+        const float s_ = dot * p.rowscale[(size_t)obj * p.stride_rs + bi];
+        p.match_idx[col] = bi;
+        p.match_corr[col] = s_ * p.colscale[col];
+    } else if (q < p.HW) {
+        const int pos = atomicAdd(p.ucount + obj, 1);
+        p.ulist[(size_t)obj * p.HW + pos] = q;
+        if (p.utotal) atomicAdd(p.utotal + obj, 1);
+    }
+}
+
+// bank_scan_finish_kernel<1> for the listed columns of bank_scan_kernel<1, 0, true> (partials at list positions)
+__global__ void bank_match_finish_listed_kernel(const float* __restrict__ part, int nsplit, int HW, int obj_n,
+                                                const int* __restrict__ ulist, const int* __restrict__ ucount,
+                                                int* __restrict__ idx, float* __restrict__ corr, const float* __restrict__ colscale) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = min(t >> 3, obj_n * HW - 1), j = t & 7;
+    const int obj = i / HW, pos = i - obj * HW;
+    const bool live = (t >> 3) < obj_n * HW && pos < ucount[obj];
+    float m = -INFINITY, x = __int_as_float(0x7fffffff);
+    auto fold = [&](float om, float ox) {
+        const int i0 = __float_as_int(x), i1 = __float_as_int(ox);
+        if (om > m || (om == m && i1 < i0)) { m = om; x = ox; }
+    };
+    if (live)
+        for (int s = j; s < nsplit; s += 8) {
+            const float* src = part + (((size_t)obj * nsplit + s) * HW + pos) * 2;
+            fold(src[0], src[1]);
+        }
+    const int base = (threadIdx.x & 63) & ~7;
+#pragma unroll
+    for (int o = 1; o < 8; ++o) {
+        const float om = __shfl(m, base + o, 64), ox = __shfl(x, base + o, 64);
+        if (j == 0) fold(om, ox);
+    }
+    if (j != 0 || !live) return;
+    const size_t c = (size_t)obj * HW + ulist[(size_t)obj * HW + pos];
+    idx[c] = __float_as_int(x);
+    corr[c] = m * colscale[c];
 }
 
 // p = exp(scale*s - m) * (1/l) for the 16 scores of a lane (branch-free: an out-of-range query carries m = +big and
@@ -1760,12 +1931,12 @@ extern "C" int vfn_bank_scan(const vfn_bankscan_desc* d, void* stream) {
         }
     }
     switch (d->mode * 3 + d->precision) {
-        case 0: hipLaunchKernelGGL((bank_scan_kernel<0, 0>), grid, dim3(256), SCAN_LDS, s, *d); break;
-        case 1: hipLaunchKernelGGL((bank_scan_kernel<0, 1>), grid, dim3(256), SCAN_LDS, s, *d); break;
-        case 2: hipLaunchKernelGGL((bank_scan_kernel<0, 2>), grid, dim3(256), SCAN_LDS, s, *d); break;
-        case 3: hipLaunchKernelGGL((bank_scan_kernel<1, 0>), grid, dim3(256), SCAN_LDS, s, *d); break;
-        case 4: hipLaunchKernelGGL((bank_scan_kernel<1, 1>), grid, dim3(256), SCAN_LDS, s, *d); break;
-        case 5: hipLaunchKernelGGL((bank_scan_kernel<1, 2>), grid, dim3(256), SCAN_LDS, s, *d); break;
+        case 0: hipLaunchKernelGGL((bank_scan_kernel<0, 0>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
+        case 1: hipLaunchKernelGGL((bank_scan_kernel<0, 1>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
+        case 2: hipLaunchKernelGGL((bank_scan_kernel<0, 2>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
+        case 3: hipLaunchKernelGGL((bank_scan_kernel<1, 0>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
+        case 4: hipLaunchKernelGGL((bank_scan_kernel<1, 1>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
+        case 5: hipLaunchKernelGGL((bank_scan_kernel<1, 2>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
         default: return VFN_ERR_ARG;
     }
     return vfn_check_launch();
@@ -1784,6 +1955,39 @@ extern "C" int vfn_bank_scan_finish(const float* part, int nsplit, int HW, int o
         hipLaunchKernelGGL(bank_scan_finish_kernel<1>, dim3(cdiv(total * 8, 256)), dim3(256), 0, (hipStream_t)stream,
                            part, nsplit, HW, obj_n, ml, idx, corr, colscale);
     }
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_bank_match_certified(const vfn_bankmatch_desc* d, void* stream) {
+    if (!d || !d->q || !d->bank_k || !d->bank_k_lp || !d->bank_len || !d->rowscale || !d->qnorm || !d->colscale) return VFN_ERR_ARG;
+    if (!d->part_x3 || !d->part_f32 || !d->ulist || !d->ucount || !d->work_counter || !d->match_idx || !d->match_corr) return VFN_ERR_ARG;
+    if (d->nsplit < 1 || d->nsplit_fb < 1 || d->HW < 1 || d->obj_n < 1 || d->ldq % 4 || d->stride_rs % 4) return VFN_ERR_ARG;
+    static bool once = false;
+    if (!once) {
+        allow_lds(bank_scan_kernel<2, 2>, SCAN_LDS); allow_lds(bank_scan_kernel<1, 0, true>, SCAN_LDS);
+        once = true;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    vfn_bankscan_desc sd = {};
+    sd.q = d->q; sd.bank_k = d->bank_k; sd.bank_len = d->bank_len; sd.rowscale = d->rowscale;
+    sd.stride_q = d->stride_q; sd.stride_k = d->stride_k; sd.stride_rs = d->stride_rs;
+    sd.scale = 1.f; sd.ldq = d->ldq; sd.q_per_obj = 1; sd.HW = d->HW; sd.obj_n = d->obj_n;
+    sd.work_counter = d->work_counter; sd.bank_k_lp = d->bank_k_lp;
+    // 1. bf16x3 scores: best / entry / runner-up per (slice, column)
+    sd.part = d->part_x3; sd.nsplit = d->nsplit; sd.mode = 2; sd.precision = 2;
+    const int items = cdiv(d->HW, QTS) * d->nsplit * d->obj_n;
+    if (hipMemsetAsync(d->work_counter, 0, sizeof(int), s) != hipSuccess) return VFN_ERR_LAUNCH;
+    if (hipMemsetAsync(d->ucount, 0, sizeof(int) * d->obj_n, s) != hipSuccess) return VFN_ERR_LAUNCH;
+    hipLaunchKernelGGL((bank_scan_kernel<2, 2>), dim3(items < 512 ? items : 512), dim3(256), SCAN_LDS, s, sd, scan_gather{});
+    // 2. certify + exact rescore; the rest onto the list
+    hipLaunchKernelGGL(bank_match_certify_kernel, dim3(cdiv(d->HW, 32), d->obj_n), dim3(64), 0, s, *d);
+    // 3. the f32 scan over the listed columns (item count read on the device: an empty list is one near-empty launch)
+    sd.part = d->part_f32; sd.nsplit = d->nsplit_fb; sd.mode = 1; sd.precision = 0; sd.bank_k_lp = nullptr;
+    if (hipMemsetAsync(d->work_counter, 0, sizeof(int), s) != hipSuccess) return VFN_ERR_LAUNCH;
+    hipLaunchKernelGGL((bank_scan_kernel<1, 0, true>), dim3(512), dim3(256), SCAN_LDS, s, sd, scan_gather{d->ulist, d->ucount});
+    hipLaunchKernelGGL(bank_match_finish_listed_kernel, dim3(cdiv(d->obj_n * d->HW * 8, 256)), dim3(256), 0, s,
+                       (const float*)d->part_f32, d->nsplit_fb, d->HW, d->obj_n, (const int*)d->ulist, (const int*)d->ucount,
+                       d->match_idx, d->match_corr, d->colscale);
     return vfn_check_launch();
 }
 

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import ptr, stream, check, BankDesc, BankScanDesc
+from ._lib import ptr, stream, check, BankDesc, BankScanDesc, BankMatchDesc
 
 DK, DV = 128, 512
 MAX_SPLIT = 20            # memory-read apply slices (o_part slabs)
@@ -40,6 +40,14 @@ def pick_scan_slices(hw, obj_n, b_upper, target_items=1536, min_chunks=8):
         return max(1, min(int(os.environ['VFN_NSPLIT_SCAN']), nchunks, MAX_SPLIT_SCAN))
     want = max(1, target_items // (qtiles * obj_n))
     return max(1, min(want, nchunks // min_chunks if nchunks >= min_chunks else 1, MAX_SPLIT_SCAN))
+
+
+def pick_fallback_slices(obj_n, b_upper, target_items=512, min_chunks=4):
+    """Bank slices of the f32 scan over the columns the certified match leaves open: their number is known on the device
+    only, and is usually one 128-column tile per object or none, so one tile per object is sliced to fill the 512 resident
+    workgroup slots (a longer list makes more items of the same size)."""
+    nchunks = max(1, (b_upper + CH - 1) // CH)
+    return max(1, min(target_items // obj_n, nchunks // min_chunks, MAX_SPLIT_SCAN))
 
 
 def pick_nsplit(hw, obj_n, b_upper, qt=QT, max_split=MAX_SPLIT):
@@ -90,6 +98,9 @@ class FeatureBank:
         self._scratch = None
         self._norms_valid = self._lp_valid = False    # bank norms on the device describe the bank as it is (carried across updates)
         self._klp = self._vlp = None  # split-bf16 image of keys / values for the reduced-precision kernels (lp_image)
+        self._kimg_valid = False      # the key half of that image is up to date (key_image: all the f32 certified match needs)
+        self._mbuf = None             # scratch of the certified match (_match_buffers)
+        self._match_updates = 0       # updates that ran the certified match (match_stats)
 
     # ------------------------------------------------------------------ storage
     def _require_gpu(self):
@@ -127,7 +138,9 @@ class FeatureBank:
         self._stats_pinned = torch.zeros(o, 4, dtype=torch.int32).pin_memory()
         self._scratch = None
         self._klp = self._vlp = None
-        self._norms_valid = self._lp_valid = False
+        self._mbuf = None
+        self._match_updates = 0
+        self._norms_valid = self._lp_valid = self._kimg_valid = False
 
     def _ensure_scratch(self):
         if self._scratch is None:
@@ -153,18 +166,54 @@ class FeatureBank:
         import os
         if os.environ.get('VFN_LP_IMAGE', '1') == '0' or self._kbuf is None:
             return None, None
+        o, cap = self.obj_n, self._cap
         if self._klp is None:
-            o, cap = self.obj_n, self._cap
             # zero-initialised, one chunk of slack: every row a kernel can address holds finite values
             self._klp = torch.zeros(o * cap * DK * 2 + CH * DK * 2, dtype=torch.int16, device=self.device)
+            self._lp_valid = self._kimg_valid = False
+        if self._vlp is None:
             self._vlp = torch.zeros(o * cap * DV * 2 + CH * DV * 2, dtype=torch.int16, device=self.device)
             self._lp_valid = False
         if not self._lp_valid:
             bd = self._bank_desc()
             check(_lib.lib().vfn_bank_refresh_lp(_lib.C.byref(bd), ptr(self._klp), ptr(self._vlp), 1, stream()),
                   'vfn_bank_refresh_lp')
-            self._lp_valid = True
+            self._lp_valid = self._kimg_valid = True
         return self._klp, self._vlp
+
+    def key_image(self):
+        """Device tensor of the keys' split-bf16 image alone (the key half of ``lp_image``, same buffer), brought up to date
+        first: what the f32 certified match reads.  No value image is built for it; ``update`` keeps the keys current as
+        ``lp_image`` is kept, and whatever invalidates one invalidates the other."""
+        if self._klp is None:
+            self._klp = torch.zeros(self.obj_n * self._cap * DK * 2 + CH * DK * 2, dtype=torch.int16, device=self.device)
+            self._lp_valid = self._kimg_valid = False
+        if not self._kimg_valid:
+            bd = self._bank_desc()
+            check(_lib.lib().vfn_bank_refresh_lp_keys(_lib.C.byref(bd), ptr(self._klp), 1, stream()), 'vfn_bank_refresh_lp_keys')
+            self._kimg_valid = True
+        return self._klp
+
+    def _match_buffers(self):
+        if self._mbuf is None:
+            o, hw, dev = self.obj_n, self._hw, self.device
+            self._mbuf = dict(part_x3=torch.empty(o, MAX_SPLIT_SCAN, hw, 4, device=dev),
+                              ulist=torch.empty(o, hw, dtype=torch.int32, device=dev),
+                              ucount=torch.zeros(o, dtype=torch.int32, device=dev),
+                              utotal=torch.zeros(o, dtype=torch.int32, device=dev))
+        return self._mbuf
+
+    def certified_match(self):
+        """Whether ``update`` matches with the certified bf16x3 scan (f32 precision; ``VFN_CERTIFIED_MATCH=0``, read at every
+        update, selects the full f32 scan -- the same results)."""
+        import os
+        return self.precision == 'fp32' and os.environ.get('VFN_CERTIFIED_MATCH', '1') != '0'
+
+    def match_stats(self):
+        """Columns the certified match could not settle from the bf16x3 scores (and scanned in f32), per object, over the
+        updates since the bank was allocated: dict(updates, columns per object, uncertain per object).  Synchronises."""
+        unc = [0] * self.obj_n if self._mbuf is None else [int(x) for x in self._mbuf['utotal'].cpu()]
+        return dict(updates=self._match_updates, columns=self._match_updates * self._hw, uncertain=unc)
 
     # ------------------------------------------------------------------ lengths
     def _sync_len(self):
@@ -222,7 +271,7 @@ class FeatureBank:
         if self._kbuf is None:
             return None
         n = self._sync_len()
-        self._norms_valid = self._lp_valid = False           # the views are writable: a caller may edit entries
+        self._norms_valid = self._lp_valid = self._kimg_valid = False           # the views are writable: a caller may edit entries
         return [self._kbuf[i, :n[i]].t() for i in range(self.obj_n)]
 
     @keys.setter
@@ -237,7 +286,7 @@ class FeatureBank:
         if self._vbuf is None:
             return None
         n = self._sync_len()
-        self._norms_valid = self._lp_valid = False
+        self._norms_valid = self._lp_valid = self._kimg_valid = False
         return [self._vbuf[i, :n[i]].t() for i in range(self.obj_n)]
 
     @values.setter
@@ -311,7 +360,7 @@ class FeatureBank:
             self._grow(need)
         self._write_columns(keys, values, lens, frame_idx, 20.0)
         self._graph_kv = None
-        self._norms_valid = self._lp_valid = False
+        self._norms_valid = self._lp_valid = self._kimg_valid = False
         self._set_lengths([lens[i] + int(keys[i].shape[1]) for i in range(self.obj_n)])
 
     def _grow(self, need):
@@ -325,7 +374,7 @@ class FeatureBank:
         self._cap = cap
         self._scratch = None
         self._klp = self._vlp = None
-        self._lp_valid = False
+        self._lp_valid = self._kimg_valid = False
         del lens
 
     def _stage_new(self, prev_key, prev_value):
@@ -377,19 +426,34 @@ class FeatureBank:
         # cosine arg-max over the bank per new feature
         b_up = self.len_upper()
         nsplit = pick_scan_slices(hw, o, b_up)
-        d = BankScanDesc()
-        d.q, d.bank_k, d.bank_len, d.rowscale, d.part = ptr(new), ptr(self._kbuf), ptr(self._len_dev), ptr(self._kinv), ptr(self._part)
-        d.stride_q, d.stride_k, d.stride_rs = hw * ld, cap * DK, cap
-        d.scale = 1.0
-        d.ldq, d.q_per_obj, d.HW, d.obj_n, d.nsplit, d.mode = ld, 1, hw, o, nsplit, 1
-        d.precision = ops.MODES[self.precision]
-        d.work_counter = ptr(self._work)
-        if d.precision:
-            klp, _ = self.lp_image()
-            d.bank_k_lp = ptr(klp) if klp is not None else None
-        check(L.vfn_bank_scan(_lib.C.byref(d), s), 'vfn_bank_scan')
-        check(L.vfn_bank_scan_finish(ptr(self._part), nsplit, hw, o, 1, None, ptr(self._midx), ptr(self._mcorr),
-                                     ptr(self._nkinv), s), 'vfn_bank_scan_finish')
+        if self.certified_match():
+            # f32 results from bf16x3 scores: certified columns rescored exactly, the rest scanned in f32 (vfn_bank_match_certified)
+            mb = self._match_buffers()
+            md = BankMatchDesc()
+            md.q, md.bank_k, md.bank_k_lp, md.bank_len = ptr(new), ptr(self._kbuf), ptr(self.key_image()), ptr(self._len_dev)
+            md.rowscale, md.qnorm, md.colscale = ptr(self._kinv), ptr(self._nknorm), ptr(self._nkinv)
+            md.part_x3, md.part_f32, md.ulist = ptr(mb['part_x3']), ptr(self._part), ptr(mb['ulist'])
+            md.ucount, md.utotal, md.work_counter = ptr(mb['ucount']), ptr(mb['utotal']), ptr(self._work)
+            md.match_idx, md.match_corr = ptr(self._midx), ptr(self._mcorr)
+            md.stride_q, md.stride_k, md.stride_rs = hw * ld, cap * DK, cap
+            md.ldq, md.HW, md.obj_n, md.nsplit = ld, hw, o, nsplit
+            md.nsplit_fb = pick_fallback_slices(o, b_up)
+            check(L.vfn_bank_match_certified(_lib.C.byref(md), s), 'vfn_bank_match_certified')
+            self._match_updates += 1
+        else:
+            d = BankScanDesc()
+            d.q, d.bank_k, d.bank_len, d.rowscale, d.part = ptr(new), ptr(self._kbuf), ptr(self._len_dev), ptr(self._kinv), ptr(self._part)
+            d.stride_q, d.stride_k, d.stride_rs = hw * ld, cap * DK, cap
+            d.scale = 1.0
+            d.ldq, d.q_per_obj, d.HW, d.obj_n, d.nsplit, d.mode = ld, 1, hw, o, nsplit, 1
+            d.precision = ops.MODES[self.precision]
+            d.work_counter = ptr(self._work)
+            if d.precision:
+                klp, _ = self.lp_image()
+                d.bank_k_lp = ptr(klp) if klp is not None else None
+            check(L.vfn_bank_scan(_lib.C.byref(d), s), 'vfn_bank_scan')
+            check(L.vfn_bank_scan_finish(ptr(self._part), nsplit, hw, o, 1, None, ptr(self._midx), ptr(self._mcorr),
+                                         ptr(self._nkinv), s), 'vfn_bank_scan_finish')
 
         # merge + append (+ evict)
         may_evict = self.class_budget < b_up + hw
@@ -417,6 +481,8 @@ class FeatureBank:
         self._norms_valid = True
         if self._klp is not None and self._lp_valid:     # re-split the merged / appended entries only
             check(L.vfn_bank_refresh_lp(_lib.C.byref(bd), ptr(self._klp), ptr(self._vlp), 0, s), 'vfn_bank_refresh_lp')
+        elif self._klp is not None and self._kimg_valid:  # (keys only: the f32 certified match keeps no value image)
+            check(L.vfn_bank_refresh_lp_keys(_lib.C.byref(bd), ptr(self._klp), 0, s), 'vfn_bank_refresh_lp_keys')
 
         self._dirty = True
         self._len_upper = [min(n + hw, cap) for n in self._len_upper]
@@ -444,7 +510,7 @@ class FeatureBank:
         bd.frame_idx, bd.ld_new, bd.voff, bd.HW, bd.obj_n, bd.cap = int(frame_idx), DK + DV, DK, hw, o, cap
         bd.rm_class, bd.rm_request = int(class_idx), int(request_n)
         check(L.vfn_bank_remove(_lib.C.byref(bd), stream()), 'vfn_bank_remove')
-        self._norms_valid = self._lp_valid = False
+        self._norms_valid = self._lp_valid = self._kimg_valid = False
         self._dirty = True
         n = self._sync_len()
         return (self.class_budget - n[class_idx]) - request_n
