@@ -27,7 +27,7 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 13
+#define VFN_ABI_VERSION 14
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
        VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9 };
 int vfn_abi_version(void);
@@ -713,6 +713,36 @@ int vfn_ln_se_gate_f32(const float* sum_px, float inv_hw, const float* w1, const
 int vfn_ln_scale_cols_f32(const float* w, const float* g, float* out, int rows, int K, void* stream);
 int vfn_ln_add_f32(const float* a, const float* b, float* out, long long n, void* stream);
 int vfn_ln_head_f32(const float* x, const float* w, float bias, float* out, long long M, int C, int ld, int prob, void* stream);
+
+/* ------------------------------------------------------------------ water level by reference object
+ * estimation/reference_tracking.py:116-218 (est_waterlevel.py --opt ref) on the tensors the frame loop holds on the device.
+ * vfn_warp_perspective_u8   cv2.warpPerspective(img, homo_mat, (W, H)) with the default flags (bilinear, constant border 0)
+ *     for uint8 [H][W][C], C = 1 (label map) or 3 (frame), to the same size; src != dst.  minv: the INVERSE of homo_mat, 9
+ *     doubles row-major on the host (the caller inverts in float64).  OpenCV's fixed-point remap, as a definition: for the
+ *     destination pixel (x, y), in float64 without fused multiply-adds, X0 = m0 x + m1 y + m2, Y0 = m3 x + m4 y + m5,
+ *     Wd = m6 x + m7 y + m8, s = Wd ? 32 / Wd : 0, X = (int) rint(clamp(X0 s, INT_MIN, INT_MAX)) (half to even), Y likewise;
+ *     sx = X >> 5, ax = X & 31, sy = Y >> 5, ay = Y & 31; out = (sum wx wy p + 512) >> 10 over the taps (sx, sy) ..
+ *     (sx+1, sy+1) with wx in {32 - ax, ax}, wy in {32 - ay, ay}; a tap outside the image counts as 0.
+ * vfn_warp_perspective_f32  the same for the loop's frame, float [3][H][W] in [0,1]: every tap is made uint8 as
+ *     vfn_overlay_u8 does it (truncation of x * 255) before it is interpolated; out float [3][H][W] = byte / 255, i.e. the
+ *     frame vfn_overlay_u8 takes (no interleaved uint8 copy on the way).
+ * vfn_waterline_scan        label uint8 [H][W] (device); keypoints int32 [R][2] = (kx, ky) on the HOST, R <= VFN_WL_MAX_REFS
+ *     (they travel as kernel arguments).  Row t of the device log int32 [T][R] receives, per reference, row - ky of the first
+ *     row > ky of column kx whose label == water_label, or -1 (also for a key point on the last row).  A key point outside
+ *     the image: VFN_ERR_ARG, never clamped.  One wavefront per reference.
+ * vfn_waterlevel_draw_u8    in place on the RGB uint8 [H][W][3] overlay of vfn_overlay_u8; boxes int32 [R][4] = (x, y, w, h) on
+ *     the HOST, w, h >= 0; row t of the device log is read on the device (no host wait).  The project's own rule (OpenCV's
+ *     thickness-2 primitives are not reproduced): box = the pixels of the closed rectangle [x, x+w] x [y, y+h] at distance 0
+ *     or 1 from its boundary, RGB (0, 200, 0); line, where the log holds d > 1 = columns kx, kx+1, rows ky .. ky+d with
+ *     kx = (int)(x + w / 2.0), ky = y + h, RGB (200, 0, 0), after all boxes; everything clipped to the image. */
+#define VFN_WL_MAX_REFS 32
+int vfn_warp_perspective_u8(const unsigned char* src, unsigned char* dst, int H, int W, int C, const double* minv,
+                            void* stream);
+int vfn_warp_perspective_f32(const float* src, float* dst, int H, int W, const double* minv, void* stream);
+int vfn_waterline_scan(const unsigned char* label, int H, int W, const int* keypoints, int R, int water_label, int* log,
+                       int T, int t, void* stream);
+int vfn_waterlevel_draw_u8(unsigned char* overlay, int H, int W, const int* boxes, int R, const int* log, int T, int t,
+                           void* stream);
 
 #ifdef __cplusplus
 }

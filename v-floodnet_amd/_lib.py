@@ -100,7 +100,7 @@ class BankDesc(C.Structure):
                 ('obj_n', C.c_int), ('cap', C.c_int), ('rm_class', C.c_int), ('rm_request', C.c_int)]
 
 
-ABI_VERSION = 13         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
+ABI_VERSION = 14         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
 DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc}     # vfn_sizeof_desc(which)
 
 
@@ -236,6 +236,10 @@ SIGNATURES = {
     'vfn_ln_add_f32': [_p, _p, _p, _ll, _p],
     'vfn_ln_head_f32': [_p, _p, _f, _p, _ll, _i, _i, _i, _p],
     'vfn_stem_wgrad_f32': [_p, _p, _p, _p, _p, _ll, _i, _i, _i, _i, _i, _i, _i, _p],
+    'vfn_warp_perspective_u8': [_p, _p, _i, _i, _i, C.POINTER(C.c_double), _p],
+    'vfn_warp_perspective_f32': [_p, _p, _i, _i, C.POINTER(C.c_double), _p],
+    'vfn_waterline_scan': [_p, _i, _i, C.POINTER(_i), _i, _i, _p, _i, _i, _p],
+    'vfn_waterlevel_draw_u8': [_p, _i, _i, C.POINTER(_i), _i, _p, _i, _i, _p],
 }
 # every symbol include/vfn_hip.h declares (checked by tests/test_abi.py)
 ALL_SYMBOLS = sorted(list(SIGNATURES) + [

@@ -755,3 +755,94 @@ def scatter_mean_launch(src, index_row, out):
     D, S = src.shape
     check(_lib.lib().vfn_scatter_mean_f32(ptr(src), src.stride(0), src.stride(1), ptr(index_row), S, ptr(out),
                                           out.stride(0), out.stride(1), D, stream()), 'vfn_scatter_mean_f32')
+
+
+# --------------------------------------------------------------------------- water level by reference object
+def _host_ints(values, cols, what):
+    """(ctypes int array, R) of an [R][cols] table of host integers."""
+    import numpy as np
+    a = np.asarray(values)
+    if a.ndim != 2 or a.shape[1] != cols or a.shape[0] < 1 or a.dtype.kind not in 'iu':
+        raise ValueError(f'{what}: expected integers [R][{cols}] with R >= 1, got {a.dtype} {a.shape}')
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a.ctypes.data_as(C.POINTER(C.c_int)), a.shape[0], a
+
+
+def inverse_homography(homo_mat):
+    """The 9 doubles vfn_warp_perspective_* take: ``numpy.linalg.inv`` of the source -> destination matrix in float64
+    (what cv2.warpPerspective does inside without WARP_INVERSE_MAP)."""
+    import numpy as np
+    m = np.asarray(homo_mat, dtype=np.float64)
+    if m.shape != (3, 3) or not np.isfinite(m).all():
+        raise ValueError(f'homography: expected a finite 3 x 3 matrix, got shape {m.shape}')
+    inv = np.ascontiguousarray(np.linalg.inv(m), dtype=np.float64).reshape(9)
+    if not np.isfinite(inv).all():
+        raise ValueError('homography: the matrix has no finite inverse')
+    return inv
+
+
+def warp_perspective_u8(img, homo_mat, out=None, inverse=None):
+    """cv2.warpPerspective(img, homo_mat, (W, H)) with default flags on the device (include/vfn_hip.h states the arithmetic).
+    ``img``: uint8 [H,W] or [H,W,C] with C = 1 / 3, or the loop's frame float32 [3,H,W] in [0,1] (every sample is made uint8
+    by truncation of x * 255 before it is interpolated; the result is float32 [3,H,W] = byte / 255, what ``overlay_device``
+    takes).  ``inverse``: the 9 doubles of ``inverse_homography(homo_mat)`` when the caller keeps them."""
+    _lib.require_gpu(img, 'warp_perspective_u8: img')
+    inv = inverse_homography(homo_mat) if inverse is None else inverse
+    minv = inv.ctypes.data_as(C.POINTER(C.c_double))
+    if not img.is_contiguous():
+        raise ValueError('warp_perspective_u8: img must be contiguous')
+    if out is None:
+        out = torch.empty_like(img)
+    if out.shape != img.shape or out.dtype != img.dtype or not out.is_contiguous() or out.data_ptr() == img.data_ptr():
+        raise ValueError('warp_perspective_u8: out must be another contiguous tensor of the shape and type of img')
+    if img.dtype == torch.float32 and img.dim() == 3 and img.shape[0] == 3:
+        _, H, W = img.shape
+        check(_lib.lib().vfn_warp_perspective_f32(ptr(img), ptr(out), H, W, minv, stream()), 'vfn_warp_perspective_f32')
+    elif img.dtype == torch.uint8 and (img.dim() == 2 or (img.dim() == 3 and img.shape[2] in (1, 3))):
+        H, W = img.shape[:2]
+        check(_lib.lib().vfn_warp_perspective_u8(ptr(img), ptr(out), H, W, 1 if img.dim() == 2 else img.shape[2], minv, stream()),
+              'vfn_warp_perspective_u8')
+    else:
+        raise ValueError(f'warp_perspective_u8: uint8 [H,W] / [H,W,1] / [H,W,3] or float32 [3,H,W], got {img.dtype} {tuple(img.shape)}')
+    return out
+
+
+def _log_args(log, t, R, what):
+    if not (log.is_cuda and log.dtype == torch.int32 and log.dim() == 2 and log.is_contiguous() and log.shape[1] == R):
+        raise ValueError(f'{what}: log must be a contiguous int32 [T][{R}] tensor on the GPU')
+    if not 0 <= int(t) < log.shape[0]:
+        raise ValueError(f'{what}: row {t} outside a log of {log.shape[0]} rows')
+
+
+def waterline_scan(label, keypoints, log, t, water_label=1):
+    """Row ``t`` of the device log int32 [T,R] := per key point (kx, ky) (host integers [R][2]) the offset row - ky of the first
+    row below it whose label is ``water_label``, or -1 (reference_tracking.py:197-204).  A key point outside the image raises
+    ``ValueError`` (the reference: IndexError).  No host synchronisation."""
+    _lib.require_gpu(label, 'waterline_scan: label')
+    if label.dtype != torch.uint8 or label.dim() != 2 or not label.is_contiguous():
+        raise ValueError('waterline_scan: label must be a contiguous uint8 [H,W] tensor')
+    H, W = label.shape
+    kp, R, a = _host_ints(keypoints, 2, 'waterline_scan: keypoints')
+    _log_args(log, t, R, 'waterline_scan')
+    if ((a[:, 0] < 0) | (a[:, 0] >= W) | (a[:, 1] < 0) | (a[:, 1] >= H)).any():
+        raise ValueError(f'waterline_scan: key point outside the {W} x {H} image: {a.tolist()}')
+    check(_lib.lib().vfn_waterline_scan(ptr(label), H, W, kp, R, int(water_label), ptr(log), log.shape[0], int(t), stream()),
+          'vfn_waterline_scan')
+    return log
+
+
+def waterlevel_draw(overlay, boxes, log, t):
+    """In place on the RGB uint8 [H,W,3] overlay: the reference boxes (host integers [R][4] = x, y, w, h) in green and, where row
+    ``t`` of the device log holds an offset d > 1, the line from the key point down to the water in red (the rule is stated
+    in include/vfn_hip.h).  The log is read on the device."""
+    _lib.require_gpu(overlay, 'waterlevel_draw: overlay')
+    if overlay.dtype != torch.uint8 or overlay.dim() != 3 or overlay.shape[2] != 3 or not overlay.is_contiguous():
+        raise ValueError('waterlevel_draw: overlay must be a contiguous uint8 [H,W,3] tensor')
+    H, W, _ = overlay.shape
+    bx, R, a = _host_ints(boxes, 4, 'waterlevel_draw: boxes')
+    _log_args(log, t, R, 'waterlevel_draw')
+    if (a[:, 2:] < 0).any() or (abs(a) > 1 << 24).any():
+        raise ValueError(f'waterlevel_draw: boxes must have w, h >= 0 and image-sized coordinates: {a.tolist()}')
+    check(_lib.lib().vfn_waterlevel_draw_u8(ptr(overlay), H, W, bx, R, ptr(log), log.shape[0], int(t), stream()),
+          'vfn_waterlevel_draw_u8')
+    return overlay

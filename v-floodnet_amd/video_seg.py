@@ -55,6 +55,11 @@ def get_args(argv=None):
                              'pil: every frame is decoded by PIL (the reference path).')
     parser.add_argument('--size', type=int, default=480, help='Short-edge size the network runs at (reference: 480).')
     parser.add_argument('--mem-every', type=int, default=1, help='Memorise every n-th frame (reference: 1).')
+    parser.add_argument('--waterlevel', action='store_true',
+                        help='Also estimate the water level by reference object (est_waterlevel.py --opt ref) in the same pass: '
+                             './output/waterlevel/<name>_ref/waterlevel.csv and, with --viz, viz/.')
+    parser.add_argument('--ref-bbox', type=str, default=None, help='Reference boxes, one "x y w h" row each (default: records/groundtruth/<name>/ref_bbox.txt).')
+    parser.add_argument('--homo-mat', type=str, default=None, help='3 x 3 homography (default: records/groundtruth/<name>/homo_mat.txt where the test name calls for calibration).')
     return parser.parse_args(argv)
 
 
@@ -522,6 +527,21 @@ def main(args, device):
         copy_stream = decode_stream = independent_stream(device, beside=[side_])
         sink = PngSink(device, writer, beside=[side_, decode_stream])
         main_stream = torch.cuda.current_stream()
+        meter = None
+        if getattr(args, 'waterlevel', False):
+            # est_waterlevel.py --opt ref in the same pass: every frame's post-processed label (and its frame, for viz/) goes to a
+            # WaterLevelMeter on the sink's stream right where it is saved; frame 0 is the given mask, as in the reference's loop
+            from . import waterlevel
+            homo_, boxes_ = waterlevel.resolve_records(args.test_name, getattr(args, 'ref_bbox', None), getattr(args, 'homo_mat', None))
+            wl_dir = os.path.join('./output/waterlevel', f'{args.test_name}_ref')
+            wl_viz = os.path.join(wl_dir, 'viz') if args.viz else None
+            os.makedirs(wl_viz or wl_dir, exist_ok=True)
+            meter = waterlevel.WaterLevelMeter(boxes_, homo_, frames_hint=len(img_list), device=device)
+
+            def wl_measure(label_, frame_, name_):
+                return waterlevel.measure_to_sink(meter, sink, label_, frame_ if args.viz else None, name_,
+                                                  os.path.join(wl_viz, f'{name_}.png') if args.viz else None)
+            wl_measure(torch.from_numpy(pred).to(device), ori_first_frame[0], first_name)
         staging = {}
         slot = [0]
         N_SLOTS = 6                              # frames t .. t+3 in flight + the one being filled + one spare
@@ -592,6 +612,8 @@ def main(args, device):
                 fo['reader_done'] = sink.save(lab, os.path.join(seg_dir, f'{name}.png'), color_palette,
                                               frame=dev_[0] if args.viz else None,
                                               overlay_path=os.path.join(overlay_dir, f'{name}.png') if args.viz else None)
+                if meter is not None:
+                    fo['reader_done'] = wl_measure(lab, dev_[0], name)
             if len(runner._gpending) == 2:
                 runner.collect_group()
         while runner._gpending:
@@ -624,6 +646,8 @@ def main(args, device):
             buf['reader_done'] = sink.save(runner.label_device(), os.path.join(seg_dir, f'{name}.png'), color_palette,
                                            frame=cur_dev[0] if args.viz else None,
                                            overlay_path=os.path.join(overlay_dir, f'{name}.png') if args.viz else None)
+            if meter is not None:
+                buf['reader_done'] = wl_measure(runner.label_device(), cur_dev[0], name)
             t3 = time.perf_counter()
             if len(runner._pending) == 2:
                 runner.collect()                 # frame t-1: its bank statistics
@@ -653,6 +677,9 @@ def main(args, device):
         if not png_decode.check_status(device):          # second line of defence: png_decode.inflate rejects such a frame itself
             raise RuntimeError('corrupt PNG frame data (invalid scanline filter type) in ' + args.test_path)
     writer.close()
+    if meter is not None:
+        meter.write_csv(os.path.join(wl_dir, 'waterlevel.csv'))
+        runner.waterlevel = meter
 
     runner.fb.print_peak_mem()
     runner.kept_labels = torch.stack(keep, 0) if keep is not None else None    # uint8 [T,H0,W0] on the device, frame 0 = given mask
