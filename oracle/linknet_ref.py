@@ -142,7 +142,8 @@ def encoder(sd, x, calibrate=False):
     return feats
 
 
-def decoder(sd, feats, calibrate=False):
+def decoder(sd, feats, calibrate=False, taps=None):
+    """``taps``: a list that receives the output of each of the five blocks (after its skip add)."""
     feats = feats[1:][::-1]                                        # drop the input, deepest first
     x, skips = feats[0], feats[1:]
     for j in range(5):
@@ -153,6 +154,8 @@ def decoder(sd, feats, calibrate=False):
         x = F.relu(_bn(F.conv2d(x, sd[p + '.2.0.weight'].to(x.dtype)), sd, p + '.2.1', BN_EPS_DEC, calibrate))
         if j < len(skips):
             x = x + skips[j]
+        if taps is not None:
+            taps.append(x)
     return x
 
 

@@ -20,7 +20,9 @@ of the reference's pickled model loads as it is; ``predict`` runs entirely in HI
 
 **Parity unpinned**: both packages and the trained weights are absent here and the reference holds no golden output for this model;
 the architecture is restated from the packages' published definitions (``oracle/linknet_ref.py`` is the same restatement in torch
-ops, which ``tests/test_linknet*.py`` compare this path with, on synthetic weights).  There is no CPU fallback.
+ops, which ``tests/test_linknet.py`` compares this path with end to end, on synthetic weights; ``tests/test_linknet_kernels_gpu.py``
+holds every kernel of ``csrc/linknet_ops.hip`` and the transposed convolution's packing + launch against float64 one by one, and
+the features of the smallest legal inputs against the oracle's).  There is no CPU fallback.
 """
 import math
 
@@ -123,6 +125,18 @@ def _pack_1x1(w, cin_p, cout_p, dev):
     return ops.pad_rows(full)
 
 
+def pack_transposed(conv_t, bn, mid_p, dev):
+    """``ConvTranspose2d(mid, mid, 4, stride 2, padding 1)`` + eval-mode BatchNorm -> (packed filters, scale, shift) of the
+    stride-1 4x4 convolution over the zero-inserted input (``vfn_dilate2_f32``; 2 zeros before, 1 after) that computes it:
+    Wc[o][i][kh][kw] = Wt[i][o][3-kh][3-kw], channels zero-padded to ``mid_p``, the transposed convolution's bias in the shift."""
+    wt = conv_t.weight.detach().float().to(dev)                    # [in, out, 4, 4]
+    mid = wt.shape[0]
+    wc = torch.zeros(mid_p, mid_p, 4, 4, device=dev)
+    wc[:mid, :mid] = wt.flip(2, 3).transpose(0, 1)
+    sc, sh = _bn_consts(bn, mid_p, dev, conv_bias=conv_t.bias)
+    return ops.pad_rows(W.pack_conv_weight(wc)), sc, sh
+
+
 class LinknetB4(nn.Module):
     def __init__(self, device=None):
         super().__init__()
@@ -211,13 +225,7 @@ class LinknetB4(nn.Module):
             q = dict(cin_p=cin_p, mid_p=mid_p, cout_p=cout_p)
             q['a_w'] = _pack_1x1(blk.block[0][0].weight, cin_p, mid_p, dev)
             q['a_sc'], q['a_sh'] = _bn_consts(blk.block[0][1], mid_p, dev)
-            # ConvTranspose2d weight [in, out, 4, 4]: the equivalent convolution over the zero-inserted input has filters
-            # Wc[o][i][kh][kw] = Wt[i][o][3-kh][3-kw]
-            wt = blk.block[1][0].weight.detach().float().to(dev)
-            wc = torch.zeros(mid_p, mid_p, 4, 4, device=dev)
-            wc[:mid, :mid] = wt.flip(2, 3).transpose(0, 1)
-            q['t_w'] = ops.pad_rows(W.pack_conv_weight(wc))
-            q['t_sc'], q['t_sh'] = _bn_consts(blk.block[1][1], mid_p, dev, conv_bias=blk.block[1][0].bias)
+            q['t_w'], q['t_sc'], q['t_sh'] = pack_transposed(blk.block[1][0], blk.block[1][1], mid_p, dev)
             q['c_w'] = _pack_1x1(blk.block[2][0].weight, mid_p, cout_p, dev)
             q['c_sc'], q['c_sh'] = _bn_consts(blk.block[2][1], cout_p, dev)
             dec.append(q)
@@ -285,7 +293,9 @@ class LinknetB4(nn.Module):
                     self._graph_runs[key] = -10 ** 9
         return self._predict_eager(P, x, logits)
 
-    def _predict_eager(self, P, x, logits):
+    def _predict_eager(self, P, x, logits, taps=None):
+        """The launches of one frame.  ``taps``: a list that receives the stem output, the four stage features and the five decoder
+        block outputs (after their skip adds) as the NHWC, channel-padded tensors the kernels wrote -- no copy (tests)."""
         L = _lib.lib()
         dev = P['dev']
         x = x.float().contiguous()
@@ -324,6 +334,8 @@ class LinknetB4(nn.Module):
             cur, h, w = out, ho, wo
             if i + 1 in STAGE_IDXS:
                 feats.append(cur)
+        if taps is not None:
+            taps.extend(feats)
         feats = feats[::-1]                                   # deepest first: 448, 160, 56, 32, 48 channels
         xd = feats[0]
         for j, q in enumerate(P['dec']):
@@ -339,6 +351,8 @@ class LinknetB4(nn.Module):
             if j + 1 < len(feats):
                 check(L.vfn_ln_add_f32(ptr(c), ptr(feats[j + 1]), ptr(c), c.numel(), stream()), 'vfn_ln_add_f32')
             xd = c
+            if taps is not None:
+                taps.append(c)
         out = f(N, 1, h, w)
         check(L.vfn_ln_head_f32(ptr(xd), ptr(P['head_w']), P['head_b'], ptr(out), N * h * w, 32, xd.shape[-1], int(not logits), stream()),
               'vfn_ln_head_f32')
