@@ -41,27 +41,6 @@ __device__ __forceinline__ int swz(int row, int chunk) { return row * DK + ((chu
 // [rows][64 floats] image (P^T): chunk index 0..15 XOR (row & 15)
 __device__ __forceinline__ int swz64(int row, int chunk) { return row * CH + ((chunk ^ (row & 15)) << 2); }
 
-// one 64 x 128 chunk = 2048 float4 = 8 per thread: global -> registers, registers -> LDS
-struct ChunkRegs { f32x4 v[8]; };
-__device__ __forceinline__ void chunk_load(ChunkRegs& R, const float* src, int valid, int tid) {
-    const int c = tid & 31;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int r = (tid >> 5) + 8 * j;
-        const int rr = r < valid ? r : 0;                         // clamp: no branch around the load
-        R.v[j] = *reinterpret_cast<const f32x4*>(src + (size_t)rr * DK + c * 4);
-        if (r >= valid) R.v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-__device__ __forceinline__ void chunk_store(const ChunkRegs& R, float* dst, int tid) {
-    const int c = tid & 31;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int r = (tid >> 5) + 8 * j;
-        *reinterpret_cast<f32x4*>(dst + swz(r, c)) = R.v[j];
-    }
-}
-
 // One 64 x 128 key chunk straight into its swizzled LDS image with LDS-DMA (no VGPRs): a wave
 // instruction writes 1 KB = two image rows linearly, so the XOR swizzle goes on the per-lane SOURCE
 // address.  Rows past `valid` re-read the last valid row (finite data; masked by the caller).
@@ -73,16 +52,6 @@ __device__ __forceinline__ void chunk_load_async(float* sK, const float* src, in
         const int rr = min(r, valid - 1);
         const float* g = src + (size_t)rr * DK + ((pc ^ (r & 15)) << 2);
         __builtin_amdgcn_global_load_lds(g, sK + (wave * 8 + j) * 2 * DK, 16, 0, 0);
-    }
-}
-
-// stage `rows` x 128 floats (row r from src + r*ld, zero past `valid` rows) into an LDS image
-__device__ __forceinline__ void stage_rows(float* dst, const float* src, size_t ld, int rows, int valid, int tid) {
-    const int c = tid & 31;
-    for (int r = tid >> 5; r < rows; r += 8) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r < valid) v = *reinterpret_cast<const f32x4*>(src + (size_t)r * ld + c * 4);
-        *reinterpret_cast<f32x4*>(dst + swz(r, c)) = v;
     }
 }
 
@@ -138,6 +107,9 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
 __device__ __forceinline__ int swzk(int row, int half, int chunk) { return row * 512 + half * 256 + ((chunk ^ (row & 15)) << 4); }   // bytes
 // rows of 256 B (query image; hi plane of a key chunk): 16-byte chunk index XOR (row & 15)
 __device__ __forceinline__ int swzq(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }          // bytes
+// P^T rows of 128 B (reduced-precision apply kernels).  k is in natural order everywhere: step g of a 32x32x16 MFMA takes
+// k = 16g + 8*(lane>>5) + j.
+__device__ __forceinline__ int swzp(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }    // bytes
 
 template <int NT, bool X3>
 __device__ __forceinline__ void convert_chunk_inplace(float* sK, int tid) {
@@ -901,13 +873,43 @@ __device__ __forceinline__ void apply_item(const vfn_memread_desc& p, int& split
     split = pair - obj * p.nsplit;
 }
 
+// ---- steps the apply kernels take the same way (128 query columns x one bank slice per workgroup, 8 waves)
+// A step is shared only where the kernel's machine code comes out the same with the call as with the block written out: these
+// kernels sit at 236-256 registers, and hipcc's register allocation follows the order in which the inliner leaves the
+// instructions.  That holds for the three helpers below (load_qstats not in memread_apply_wide_kernel, zero_o only in the wide
+// and shw kernels).  The query image, the P^T store, the hit-count bump and the o_part epilogue changed the instruction stream
+// of every kernel they were shared between and stay written out; a change to one of those conventions goes to every apply kernel.
+constexpr int QTW = 128;    // query columns per apply workgroup
+// this workgroup's item: first query column and bank length
+__device__ __forceinline__ void apply_slice(const vfn_memread_desc& p, int& split, int& qt, int& obj, int& q0, int& B) {
+    apply_item(p, split, qt, obj);
+    q0 = qt * QTW;
+    B = p.bank_len[obj];
+}
+
+// softmax statistics of query column q0 + qcol: (m, 1/l); a column past HW carries m = +big, 1/l = 0 (p = 0 exactly)
+__device__ __forceinline__ void load_qstats(const vfn_memread_desc& p, int obj, int q0, int qcol, float& qm, float& qinv) {
+    qm = 1e30f; qinv = 0.f;
+    if (q0 + qcol < p.HW) {
+        qm = p.ml[((size_t)obj * p.HW + q0 + qcol) * 2];
+        qinv = 1.f / p.ml[((size_t)obj * p.HW + q0 + qcol) * 2 + 1];
+    }
+}
+
+// O^T accumulators of a wave: TQN query tiles x TCN channel tiles of 32 x 32
+template <int TQN, int TCN>
+__device__ __forceinline__ void zero_o(f32x16 (&o)[TQN][TCN]) {
+#pragma unroll
+    for (int a = 0; a < TQN; ++a)
+#pragma unroll
+        for (int b = 0; b < TCN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
+}
+
 // ------------------------------------------------------------------ pass 2: P^T V and hit counts
 // (The 64-query apply kernels of rounds 1-2 are gone: the 128-query kernels below measured faster at every bank size in
 // every precision mode and were the only ones the default path had selected since.)
-// LDS swizzles of the reduced-precision kernels (bytes): query image rows of 256 B, P^T rows of 128 B.  k is in natural
-// order everywhere: step g of a 32x32x16 MFMA takes k = 16g + 8*(lane>>5) + j.
-__device__ __forceinline__ int swzp(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }    // bytes
-
 // ------------------------------------------------------------------ pass 2, bf16 / bf16x3, wide query tile
 // For the bandwidth-bound regime (reduced-precision MFMAs are 5-16x faster than the f32 ones, so streaming the bank
 // becomes the cost; at the C5 sizes every query tile re-reads a multi-GB bank): 128 query columns per workgroup,
@@ -915,8 +917,6 @@ __device__ __forceinline__ int swzp(int row, int chunk) { return row * 128 + ((c
 // wave w owns value channels 64w..64w+63 for all 128 queries, so no value row is loaded or converted twice.
 // LDS: query image bf16 hi/lo [128][128] (32 + 32 KB), key chunk f32 [64][128] (32 KB), P^T bf16 hi/lo [128 q][64 b]
 // (16 + 16 KB): 128 KB for bf16x3, one workgroup per CU (8 waves = two per SIMD, as the other kernels).
-constexpr int QTW = 128;
-
 __device__ __forceinline__ void chunk_load_async8(float* sK, const float* src, int valid, int wave, int lane) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                    // 8 waves x 4 instructions x 2 rows = 64 rows
@@ -941,10 +941,8 @@ void memread_apply_lpw_kernel(const vfn_memread_desc p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int wr = wave >> 2, wq = wave & 3;                  // score tile: key rows 32wr.., query columns 32wq..
-    int split, qt, obj;
-    apply_item(p, split, qt, obj);
-    const int q0 = qt * QTW;
-    const int B = p.bank_len[obj];
+    int split, qt, obj, q0, B;
+    apply_slice(p, split, qt, obj, q0, B);
     const float* K = p.bank_k + (size_t)obj * p.stride_k;
     const float* V = p.bank_v + (size_t)obj * p.stride_v;
 
@@ -974,19 +972,14 @@ void memread_apply_lpw_kernel(const vfn_memread_desc p) {
             for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
 
     // value channels of this wave: 64*wave .. +63; lane li owns channels 2*li, 2*li+1 (one per 32-wide tile tc)
-    const float* vcol = V + wave * 64 + li * 2;               // + row*512
     const unsigned vlane_off = (unsigned)((8 * lh) * DV + wave * 64 + li * 2) * 4u;   // bytes, per lane
 
     if (c_lo < c_hi) chunk_load_async8(sK, K + (size_t)c_lo * CH * DK, min(CH, B - c_lo * CH), wave, lane);
     __syncthreads();
 
     const int qcol = wq * 32 + li;
-    const bool qok = (q0 + qcol) < p.HW;
-    float qm = 1e30f, qinv = 0.f;
-    if (qok) {
-        qm = p.ml[((size_t)obj * p.HW + q0 + qcol) * 2];
-        qinv = 1.f / p.ml[((size_t)obj * p.HW + q0 + qcol) * 2 + 1];
-    }
+    float qm, qinv;
+    load_qstats(p, obj, q0, qcol, qm, qinv);
 
     for (int c = c_lo; c < c_hi; ++c) {
         const int b0 = c * CH;
@@ -1108,10 +1101,8 @@ void memread_apply_shw_kernel(const vfn_memread_desc p) {
     const int li = lane & 31, lh = lane >> 5;
     const int wr = wave >> 2, wq = wave & 3;                  // score tile: key rows 32wr.., query columns 32wq..
     const int qhalf = wave >> 2, cq = wave & 3;               // P^T V: queries 64qhalf.., channels 128cq..
-    int split, qt, obj;
-    apply_item(p, split, qt, obj);
-    const int q0 = qt * QTW;
-    const int B = p.bank_len[obj];
+    int split, qt, obj, q0, B;
+    apply_slice(p, split, qt, obj, q0, B);
     const float* K = reinterpret_cast<const float*>(p.bank_k_lp) + (size_t)obj * p.stride_k;     // image rows are 512 B too
     const char* V = reinterpret_cast<const char*>(p.bank_v_lp) + (size_t)obj * p.stride_v * 4;   // blocks of 8 rows, 16 KB
 
@@ -1133,12 +1124,7 @@ void memread_apply_shw_kernel(const vfn_memread_desc p) {
     chunk_range(B, p.nsplit, split, c_lo, c_hi);
 
     f32x16 o[2][4];                                           // O^T tiles: [query tile][channel tile]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
+    zero_o(o);
 
     const unsigned vlane_off = (unsigned)lh * VBLK + (unsigned)(cq * 128 + li) * 16u;   // bytes, per lane: row block lh of a step
 
@@ -1146,12 +1132,8 @@ void memread_apply_shw_kernel(const vfn_memread_desc p) {
     __syncthreads();
 
     const int qcol = wq * 32 + li;
-    const bool qok = (q0 + qcol) < p.HW;
-    float qm = 1e30f, qinv = 0.f;
-    if (qok) {
-        qm = p.ml[((size_t)obj * p.HW + q0 + qcol) * 2];
-        qinv = 1.f / p.ml[((size_t)obj * p.HW + q0 + qcol) * 2 + 1];
-    }
+    float qm, qinv;
+    load_qstats(p, obj, q0, qcol, qm, qinv);
 
     for (int c = c_lo; c < c_hi; ++c) {
         const int b0 = c * CH;
@@ -1307,10 +1289,8 @@ void memread_apply_pipe_kernel(const vfn_memread_desc p) {
     constexpr int TQN = 4, TCN = 2;
     const int qbase = 0, cbase = wave * 64;
 #endif
-    int split, qt, obj;
-    apply_item(p, split, qt, obj);
-    const int q0 = qt * QTW;
-    const int B = p.bank_len[obj];
+    int split, qt, obj, q0, B;
+    apply_slice(p, split, qt, obj, q0, B);
     const char* Kimg = reinterpret_cast<const char*>(p.bank_k_lp) + (size_t)obj * p.stride_k * 4;   // image rows of 512 B: [128 hi | 128 lo]
     const char* V = reinterpret_cast<const char*>(p.bank_v_lp) + (size_t)obj * p.stride_v * 4;      // blocks of 8 rows, 16 KB
 
@@ -1337,12 +1317,8 @@ void memread_apply_pipe_kernel(const vfn_memread_desc p) {
             for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
 
     const int qcol = wq * 32 + li;
-    const bool qok = (q0 + qcol) < p.HW;
-    float qm = 1e30f, qinv = 0.f;
-    if (qok) {
-        qm = p.ml[((size_t)obj * p.HW + q0 + qcol) * 2];
-        qinv = 1.f / p.ml[((size_t)obj * p.HW + q0 + qcol) * 2 + 1];
-    }
+    float qm, qinv;
+    load_qstats(p, obj, q0, qcol, qm, qinv);
     const float sm = -qm;
     const int rloc = wr * 32 + 4 * lh;                        // this lane's first score row inside a chunk (+ (r & 3) + 8 (r >> 2))
 
@@ -1580,14 +1556,12 @@ void memread_apply_wide_kernel(const vfn_memread_desc p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int wr = wave >> 2, wq = wave & 3;
-    int split, qt, obj;
-    apply_item(p, split, qt, obj);
-    const int q0 = qt * QTW;
-    const int B = p.bank_len[obj];
+    int split, qt, obj, q0, B;
+    apply_slice(p, split, qt, obj, q0, B);
     const float* K = p.bank_k + (size_t)obj * p.stride_k;
     const float* V = p.bank_v + (size_t)obj * p.stride_v;
 
-    {   // query image (zero past HW)
+    {   // query image (zero past HW): f32 rows under swz
         const int c = tid & 31;
         for (int r = tid >> 5; r < QTW; r += 16) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -1600,20 +1574,17 @@ void memread_apply_wide_kernel(const vfn_memread_desc p) {
     chunk_range(B, p.nsplit, split, c_lo, c_hi);
 
     f32x16 o[4][2];                                  // O^T tiles: [query tile][channel tile]
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
+    zero_o(o);
 
-    const float* vcol = V + wave * 64 + li * 2;      // + row*512; lane li owns channels 2*li, 2*li+1 (tile tc)
+    // lane li owns channels 2*li, 2*li+1 (tile tc) of the wave's 64.  (vcol is unused, but the kernel's register allocation changes without it)
+    const float* vcol = V + wave * 64 + li * 2;
     const unsigned vlane_off = (unsigned)((4 * lh) * DV + wave * 64 + li * 2) * 4u;   // bytes, per lane
 
     if (c_lo < c_hi) chunk_load_async8(sK, K + (size_t)c_lo * CH * DK, min(CH, B - c_lo * CH), wave, lane);
     __syncthreads();
 
     const int qcol = wq * 32 + li;
+    // (written out: load_qstats changes this kernel's register allocation)
     const bool qok = (q0 + qcol) < p.HW;
     float qm = 1e30f, qinv = 0.f;
     if (qok) {
@@ -1722,11 +1693,9 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int wr = wave >> 2, wq = wave & 3;
-    int split, qt, obj;
-    apply_item(p, split, qt, obj);
-    const int q0 = qt * QTW;
+    int split, qt, obj, q0, B;
+    apply_slice(p, split, qt, obj, q0, B);
     const int qtiles = (p.HW + QTW - 1) / QTW;
-    const int B = p.bank_len[obj];
     const float* V = p.bank_v + (size_t)obj * p.stride_v;
     const float* S = p.scores + (size_t)obj * p.stride_scores;
 
@@ -1741,7 +1710,7 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
 
-    const float* vcol = V + wave * 64 + li * 2;      // + row*512; lane li owns channels 2*li, 2*li+1 (tile tc)
+    // lane li owns channels 2*li, 2*li+1 (tile tc) of the wave's 64
     const unsigned vlane_off = (unsigned)((4 * lh) * DV + wave * 64 + li * 2) * 4u;   // bytes, per lane
     // this lane's 16 scores of a chunk: key rows 32wr + (r&3) + 8(r>>2) + 4lh, query column 32wq + li
     const unsigned slane_off = (unsigned)(((wr * 4) * 2 + lh) * QTW + wq * 32 + li) * 16u;      // bytes; + g * 2 * QTW * 16
@@ -1752,12 +1721,8 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
         for (int g = 0; g < 4; ++g) sv[g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(tile + slane_off + g * (2 * QTW * 16)));
     };
     const int qcol = wq * 32 + li;
-    const bool qok = (q0 + qcol) < p.HW;
-    float qm = 1e30f, qinv = 0.f;
-    if (qok) {
-        qm = p.ml[((size_t)obj * p.HW + q0 + qcol) * 2];
-        qinv = 1.f / p.ml[((size_t)obj * p.HW + q0 + qcol) * 2 + 1];
-    }
+    float qm, qinv;
+    load_qstats(p, obj, q0, qcol, qm, qinv);
     const int rloc = wr * 32 + 4 * lh;
     // softmax of chunk c from the loaded scores -> P^T buffer `buf`, hit counts
     auto softmax_to = [&](int c, float* sPb) {
@@ -1896,6 +1861,12 @@ void allow_lds(K kern, size_t bytes) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// an integer switch from the environment; unset -> dflt
+int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 }  // namespace
 
 extern "C" int vfn_bank_scan(const vfn_bankscan_desc* d, void* stream) {
@@ -1904,40 +1875,39 @@ extern "C" int vfn_bank_scan(const vfn_bankscan_desc* d, void* stream) {
     if (d->mode == 1 && (!d->rowscale || d->stride_rs % 4)) return VFN_ERR_ARG;
     if (d->precision < 0 || d->precision > 2) return VFN_ERR_ARG;
     if (d->scores && (d->mode != 0 || !scores_fit(d->stride_scores, d->stride_k, d->HW))) return VFN_ERR_ARG;
-    static bool once = false;
-    if (!once) {
+    // one-time set-up: LDS limits of every kernel this launcher can pick (the register-staged kernels fit the default limit), and
+    // VFN_SCAN_WGS: 32 KB of LDS and <= 160 registers -- three register-staged workgroups fit a CU (the queue feeds any number)
+    static const int pipe_wgs = [] {
         allow_lds(bank_scan_kernel<0, 0>, SCAN_LDS); allow_lds(bank_scan_kernel<1, 0>, SCAN_LDS);
         allow_lds(bank_scan_kernel<0, 1>, SCAN_LDS); allow_lds(bank_scan_kernel<1, 1>, SCAN_LDS);
         allow_lds(bank_scan_kernel<0, 2>, SCAN_LDS); allow_lds(bank_scan_kernel<1, 2>, SCAN_LDS);
-        once = true;
-    }
+        const int wgs = env_int("VFN_SCAN_WGS", 768);
+        return wgs < 1 ? 768 : wgs;
+    }();
     if (!d->work_counter) return VFN_ERR_ARG;
     const int items = cdiv(d->HW, QTS) * d->nsplit * d->obj_n;
-    const dim3 grid(items < 512 ? items : 512);        // two resident workgroups per CU (64 KB of LDS each)
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d->work_counter, 0, sizeof(int), s) != hipSuccess) return VFN_ERR_LAUNCH;
-    if (d->precision == 1 && d->bank_k_lp) {
-        // plain bf16 on the kept key image (round 6): keys through registers, two chunks ahead; VFN_SCAN_PIPE=0 (read at every
-        // call: A/B in one process) restores bank_scan_kernel<MODE, 1>
-        const char* ep = getenv("VFN_SCAN_PIPE");
-        if (!(ep && atoi(ep) == 0)) {
-            // 32 KB of LDS and <= 160 registers: three workgroups fit a CU (the queue feeds any number of them)
-            static int wgs = 0;
-            if (!wgs) { const char* ew = getenv("VFN_SCAN_WGS"); wgs = ew ? atoi(ew) : 768; if (wgs < 1) wgs = 768; }
-            const dim3 gridp(items < wgs ? items : wgs);
-            if (d->mode == 0) hipLaunchKernelGGL((bank_scan_pipe_kernel<0>), gridp, dim3(256), SCAN_PIPE_LDS, s, *d);
-            else hipLaunchKernelGGL((bank_scan_pipe_kernel<1>), gridp, dim3(256), SCAN_PIPE_LDS, s, *d);
-            return vfn_check_launch();
-        }
-    }
-    switch (d->mode * 3 + d->precision) {
-        case 0: hipLaunchKernelGGL((bank_scan_kernel<0, 0>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        case 1: hipLaunchKernelGGL((bank_scan_kernel<0, 1>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        case 2: hipLaunchKernelGGL((bank_scan_kernel<0, 2>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        case 3: hipLaunchKernelGGL((bank_scan_kernel<1, 0>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        case 4: hipLaunchKernelGGL((bank_scan_kernel<1, 1>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        case 5: hipLaunchKernelGGL((bank_scan_kernel<1, 2>), grid, dim3(256), SCAN_LDS, s, *d, scan_gather{}); break;
-        default: return VFN_ERR_ARG;
+    // plain bf16 on the kept key image (round 6): keys through registers, two chunks ahead; VFN_SCAN_PIPE=0 (read at every
+    // call: A/B in one process) restores bank_scan_kernel<MODE, 1>
+    const bool pipe = d->precision == 1 && d->bank_k_lp && env_int("VFN_SCAN_PIPE", 1) != 0;
+    // otherwise two resident workgroups per CU (64 KB of LDS each)
+    const int wgs = pipe ? pipe_wgs : 512;
+    const dim3 grid(items < wgs ? items : wgs), block(256);
+    auto scan = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, SCAN_LDS, s, *d, scan_gather{}); };
+    if (pipe) {
+        if (d->mode == 0) hipLaunchKernelGGL((bank_scan_pipe_kernel<0>), grid, block, SCAN_PIPE_LDS, s, *d);
+        else hipLaunchKernelGGL((bank_scan_pipe_kernel<1>), grid, block, SCAN_PIPE_LDS, s, *d);
+    } else if (d->mode == 0) {
+        if (d->precision == 0) scan(bank_scan_kernel<0, 0>);
+        else if (d->precision == 1) scan(bank_scan_kernel<0, 1>);
+        else scan(bank_scan_kernel<0, 2>);
+    } else if (d->mode == 1) {
+        if (d->precision == 0) scan(bank_scan_kernel<1, 0>);
+        else if (d->precision == 1) scan(bank_scan_kernel<1, 1>);
+        else scan(bank_scan_kernel<1, 2>);
+    } else {
+        return VFN_ERR_ARG;
     }
     return vfn_check_launch();
 }
@@ -1962,11 +1932,11 @@ extern "C" int vfn_bank_match_certified(const vfn_bankmatch_desc* d, void* strea
     if (!d || !d->q || !d->bank_k || !d->bank_k_lp || !d->bank_len || !d->rowscale || !d->qnorm || !d->colscale) return VFN_ERR_ARG;
     if (!d->part_x3 || !d->part_f32 || !d->ulist || !d->ucount || !d->work_counter || !d->match_idx || !d->match_corr) return VFN_ERR_ARG;
     if (d->nsplit < 1 || d->nsplit_fb < 1 || d->HW < 1 || d->obj_n < 1 || d->ldq % 4 || d->stride_rs % 4) return VFN_ERR_ARG;
-    static bool once = false;
-    if (!once) {
+    static const bool ready = [] {
         allow_lds(bank_scan_kernel<2, 2>, SCAN_LDS); allow_lds(bank_scan_kernel<1, 0, true>, SCAN_LDS);
-        once = true;
-    }
+        return true;
+    }();
+    (void)ready;
     hipStream_t s = (hipStream_t)stream;
     vfn_bankscan_desc sd = {};
     sd.q = d->q; sd.bank_k = d->bank_k; sd.bank_len = d->bank_len; sd.rowscale = d->rowscale;
@@ -1996,59 +1966,50 @@ extern "C" int vfn_memread_apply(const vfn_memread_desc* d, void* stream) {
     if (d->nsplit < 1 || d->ldq % 4) return VFN_ERR_ARG;
     if (d->precision < 0 || d->precision > 2) return VFN_ERR_ARG;
     if (d->scores && !scores_fit(d->stride_scores, d->stride_k, d->HW)) return VFN_ERR_ARG;
-    {
-        static bool once_x = false;
-        if (!once_x) {
-            const char* e = getenv("VFN_APPLY_XCD");
-            const int lin = (e && atoi(e) == 0) ? 1 : 0;
-            if (lin && hipMemcpyToSymbol(HIP_SYMBOL(vfn_apply_linear_order), &lin, sizeof(int)) != hipSuccess) return VFN_ERR_LAUNCH;
-            once_x = true;
-        }
-    }
+    constexpr size_t LDS_WF = (size_t)(QTW * DK + CH * DK + QTW * CH) * sizeof(float);                       // 128 KB
+    constexpr size_t LDS_SS = (size_t)2 * QTW * CH * sizeof(float);                                          // 64 KB
+    constexpr size_t LDS_W1 = (size_t)QTW * DK * 2 + (size_t)CH * DK * 4 + 2 * (size_t)QTW * CH * 2;         // 80 KB
+    constexpr size_t LDS_W2 = LDS_W1 + (size_t)QTW * DK * 2;                                                // 112 KB
+    // one-time set-up: LDS limits of every kernel this launcher can pick (memread_apply_ss_kernel fits the default limit) and the
+    // read-once switches.  VFN_APPLY_XCD=0: linear workgroup order (apply_item).  VFN_APPLY_IMG_BF16=0: plain bf16 reads the f32
+    // rows although the bank carries its split image.
+    struct setup_t { int status; bool img_bf16; };
+    static const setup_t setup = [] {
+        allow_lds(memread_apply_wide_kernel, LDS_WF);
+        allow_lds(memread_apply_lpw_kernel<false>, LDS_W1); allow_lds(memread_apply_lpw_kernel<true>, LDS_W2);
+        allow_lds(memread_apply_shw_kernel<false>, LDS_W1); allow_lds(memread_apply_shw_kernel<true>, LDS_W2);
+        allow_lds(memread_apply_pipe_kernel, APPLY_PIPE_LDS);
+        const int lin = env_int("VFN_APPLY_XCD", 1) == 0 ? 1 : 0;
+        const bool ok = !lin || hipMemcpyToSymbol(HIP_SYMBOL(vfn_apply_linear_order), &lin, sizeof(int)) == hipSuccess;
+        return setup_t{ok ? VFN_OK : VFN_ERR_LAUNCH, env_int("VFN_APPLY_IMG_BF16", 1) != 0};
+    }();
+    if (setup.status != VFN_OK) return setup.status;
+
+    // precision, image present, pipe switch -> kernel, LDS bytes
+    //   f32            scores stored by the scan ? ss : wide
+    //   bf16x3         split image ? shw<true> : lpw<true>
+    //   bf16           split image ? (VFN_APPLY_PIPE, read at every call: A/B in one process) ? pipe : shw<false>
+    //                              : lpw<false>
+    // The kept split image: keys land in LDS as the operand image, value operands come straight from the 8-row-blocked image
+    // (bank.hip) -- in plain bf16 only its hi plane is read (2 bytes per element instead of the f32 rows' 4).
+    const bool image = d->bank_k_lp && d->bank_v_lp && (d->precision == 2 || setup.img_bf16);
+    void (*kern)(const vfn_memread_desc);
+    size_t lds;
     if (d->precision == 0) {
-        static bool once_f = false;
-        constexpr size_t LDS_WF = (size_t)(QTW * DK + CH * DK + QTW * CH) * sizeof(float);       // 128 KB
-        if (!once_f) { allow_lds(memread_apply_wide_kernel, LDS_WF); once_f = true; }
-        const dim3 gridw(cdiv(d->HW, QTW) * d->nsplit, d->obj_n);
-        if (d->scores) hipLaunchKernelGGL(memread_apply_ss_kernel, gridw, dim3(512), (size_t)2 * QTW * CH * sizeof(float), (hipStream_t)stream, *d);
-        else hipLaunchKernelGGL(memread_apply_wide_kernel, gridw, dim3(512), LDS_WF, (hipStream_t)stream, *d);
-        return vfn_check_launch();
+        if (d->scores) { kern = memread_apply_ss_kernel; lds = LDS_SS; }
+        else { kern = memread_apply_wide_kernel; lds = LDS_WF; }
+    } else if (d->precision == 2) {
+        kern = image ? memread_apply_shw_kernel<true> : memread_apply_lpw_kernel<true>; lds = LDS_W2;
+    } else if (!image) {
+        kern = memread_apply_lpw_kernel<false>; lds = LDS_W1;
+    } else if (env_int("VFN_APPLY_PIPE", 1) != 0) {
+        kern = memread_apply_pipe_kernel; lds = APPLY_PIPE_LDS;
+    } else {
+        kern = memread_apply_shw_kernel<false>; lds = LDS_W1;
     }
-    {
-        static bool once_w = false;
-        constexpr size_t LDS_W1 = (size_t)QTW * DK * 2 + (size_t)CH * DK * 4 + 2 * (size_t)QTW * CH * 2;         // 80 KB
-        constexpr size_t LDS_W2 = LDS_W1 + (size_t)QTW * DK * 2;                                                // 112 KB + 16
-        if (!once_w) { allow_lds(memread_apply_lpw_kernel<false>, LDS_W1); allow_lds(memread_apply_lpw_kernel<true>, LDS_W2); once_w = true; }
-        const dim3 gridw(cdiv(d->HW, QTW) * d->nsplit, d->obj_n);
-        // bf16x3 only: in plain bf16 the image's 8-byte hi halves sit 16 bytes apart and the kernel measured 11 % slower
-        // than the f32 rows rounded in registers (9.9 vs 8.9 ms at 1.2M entries)
-        // the kept split image: keys land in LDS as the operand image, value operands come straight from the 8-row-blocked
-        // image (bank.hip) -- in plain bf16 only its hi plane is read (2 bytes per element instead of the f32 rows' 4)
-        static int img_bf16 = 1;
-        if (d->bank_k_lp && d->bank_v_lp && (d->precision == 2 || img_bf16)) {
-            static bool once_s = false;
-            if (!once_s) {
-                allow_lds(memread_apply_shw_kernel<true>, LDS_W2);
-                allow_lds(memread_apply_shw_kernel<false>, LDS_W1);
-                const char* e = getenv("VFN_APPLY_IMG_BF16");
-                if (e) img_bf16 = atoi(e);
-                once_s = true;
-            }
-            // plain bf16 (round 6): the software-pipelined kernel; VFN_APPLY_PIPE=0 (read at every call: A/B in one process) restores
-            // memread_apply_shw_kernel<false>
-            static bool once_p = false;
-            if (!once_p) { allow_lds(memread_apply_pipe_kernel, APPLY_PIPE_LDS); once_p = true; }
-            const char* ep = getenv("VFN_APPLY_PIPE");
-            const bool pipe = !(ep && atoi(ep) == 0);
-            if (d->precision == 2) hipLaunchKernelGGL(memread_apply_shw_kernel<true>, gridw, dim3(512), LDS_W2, (hipStream_t)stream, *d);
-            else if (img_bf16 && pipe) hipLaunchKernelGGL(memread_apply_pipe_kernel, gridw, dim3(512), APPLY_PIPE_LDS, (hipStream_t)stream, *d);
-            else if (img_bf16) hipLaunchKernelGGL(memread_apply_shw_kernel<false>, gridw, dim3(512), LDS_W1, (hipStream_t)stream, *d);
-            if (d->precision == 2 || img_bf16) return vfn_check_launch();
-        }
-        if (d->precision == 1) hipLaunchKernelGGL(memread_apply_lpw_kernel<false>, gridw, dim3(512), LDS_W1, (hipStream_t)stream, *d);
-        else hipLaunchKernelGGL(memread_apply_lpw_kernel<true>, gridw, dim3(512), LDS_W2, (hipStream_t)stream, *d);
-        return vfn_check_launch();
-    }
+    const dim3 grid(cdiv(d->HW, QTW) * d->nsplit, d->obj_n);
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, *d);
+    return vfn_check_launch();
 }
 
 extern "C" int vfn_memread_finish(const vfn_memread_desc* d, void* stream) {
