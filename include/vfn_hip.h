@@ -27,7 +27,7 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 14
+#define VFN_ABI_VERSION 15
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
        VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9 };
 int vfn_abi_version(void);
@@ -98,9 +98,13 @@ typedef struct vfn_conv_desc {
 
 int vfn_conv_cfg_count(void);
 int vfn_conv_cfg_tile(int cfg, int* bm, int* bn);
-/* tile configuration cfg: workgroup tile bm x bn, wm x wn waves, dma = 0 register-staged / 2 LDS-DMA ring;
- * the kernel it launches is conv_igemm_kernel<bm, bn, wm, wn, MODE> (conv_igemm_dma_kernel<bm, bn, wm, wn, dma>) */
+/* tile configuration cfg: workgroup tile bm x bn, wm x wn waves, dma = 0 register-staged / 2 LDS-DMA ring / 9 wave-autonomous
+ * or stream-K (vfn_conv_cfg_kind 1 / 2; wm = wn = 0).  Kind 0 launches conv_igemm_kernel<bm, bn, wm, wn, MODE>,
+ * conv_igemm_dma_kernel<bm, bn, wm, wn, dma>, or conv_igemm_wk_kernel where vfn_conv_cfg_wk / _tpb say so.  Non-zero: no such cfg */
 int vfn_conv_cfg_info(int cfg, int* bm, int* bn, int* wm, int* wn, int* dma);
+/* (ABI 15) arithmetic modes that accept configuration cfg, as a bit mask: bit 0 vfn_conv2d_nhwc_f32, bit 1 _bf16, bit 2 _bf16x3.
+ * An entry point returns VFN_ERR_ARG for a cfg whose bit is clear.  0: no such cfg */
+int vfn_conv_cfg_modes(int cfg);
 /* K groups per workgroup of configuration cfg: 1 for the plain ones; > 1: split-K inside the workgroup --
  * that many copies of the wm x wn wave grid each take a slice of K of the same output tile and the partial sums are
  * added through LDS in group order (conv_igemm_wk_kernel<bm, bn, wm, wn, wk>); ksplit must be <= 1 with these.  0: no such cfg */
@@ -123,12 +127,12 @@ int vfn_conv_cfg_name(int cfg, char* buf, int n);
 int vfn_conv2d_nhwc_f32(const vfn_conv_desc* d, int cfg, void* stream);
 /* Same convolution with both operands rounded to bf16 (nearest-even) as they are staged into LDS and multiplied
  * on v_mfma_f32_32x32x16_bf16 with f32 accumulation; tensors stay f32 in HBM.  Cin must be a multiple of 64;
- * register-staged tile configurations only (cfg 0-10, 17, 19); split-K slices are 64-channel tiles.
+ * register-staged tile configurations only (cfg with bit 1 of vfn_conv_cfg_modes); split-K slices are 64-channel tiles.
  * For BASELINE.json configs C3 / C5 (the reference itself has no reduced-precision path). */
 int vfn_conv2d_nhwc_bf16(const vfn_conv_desc* d, int cfg, void* stream);
 /* "bf16x3": every operand is split into two bf16 (x = hi + lo, 16 significant bits) as it is staged and each product
  * is hi*hi + hi*lo + lo*hi on the bf16 matrix cores, f32 accumulation: relative error ~2^-16 per product (bf16: 2^-9,
- * f32: 2^-24).  Cin multiple of 32, split-K slices are 32-channel tiles (as the f32 kernel); cfg as for _bf16. */
+ * f32: 2^-24).  Cin multiple of 32, split-K slices are 32-channel tiles (as the f32 kernel); cfg with bit 2 of vfn_conv_cfg_modes. */
 int vfn_conv2d_nhwc_bf16x3(const vfn_conv_desc* d, int cfg, void* stream);
 
 /* ------------------------------------------------------------------ Winograd F(4x4, 3x3) around the matrix kernels (ABI 10)

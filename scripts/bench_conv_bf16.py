@@ -33,7 +33,7 @@ for (N, H, W, Cin, Cout, k, s) in SHAPES:
     fl = 2.0 * d.M * Cout * k * k * Cin
     best32 = min(timeit(lambda: ops.conv2d_launch(d, c)) for c in (0, 2, 3, 8, 9, 10) if not (tiles[c][1] > 64 and Cout <= 32))
     line = f'M={d.M:6d} Cout={Cout:4d} K={k*k*Cin:5d} f32 best {fl/best32/1e6:5.1f} ({best32:6.1f}us) | mode {MODE}: '
-    for c in ops.BF16_CFGS:
+    for c in ops.conv_cfgs(MODE):
         bm, bn = tiles[c]
         if (bn > 64 and Cout <= 32) or (bn > 128 and Cout < 256):
             continue

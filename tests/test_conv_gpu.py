@@ -135,7 +135,7 @@ def test_conv_reduced_precision_matches_emulation(gpu, case, mode):
     resd = res.permute(0, 2, 3, 1).contiguous().to(gpu) if use_res else None
     tiles = ops.conv_cfg_tiles()
     tol = 2e-4 * max(1.0, ref.abs().max().item())
-    for cfg in ops.BF16_CFGS:
+    for cfg in ops.conv_cfgs(mode):
         if wp.shape[0] < ((Cout + tiles[cfg][1] - 1) // tiles[cfg][1]) * tiles[cfg][1]:
             continue
         y = ops.conv2d_nhwc(xd, wp, Cout, k, k, s, k // 2, scale_d, shift_d, resd, relu_in, relu_out, cfg=cfg, mode=mode)
@@ -164,6 +164,33 @@ def test_conv_reduced_precision_matches_emulation(gpu, case, mode):
         torch.cuda.synchronize()
         err = (y.permute(0, 3, 1, 2).cpu() - ref).abs().max().item()
         assert err < tol, f'split {ks}: max err {err}'
+
+
+@pytest.mark.parametrize('mode', [1, 2])
+def test_reduced_precision_refuses_the_f32_only_configurations(gpu, mode):
+    """A reduced-precision entry point launches exactly the configurations whose vfn_conv_cfg_modes bit it owns: every other id in
+    0..61 (LDS-DMA staging, the f32-only tiles, the wave-autonomous and stream-K kernels) is refused before anything is launched.
+    The tensors are valid for every tile, so a wrong dispatch would still be a well-formed launch."""
+    from vfloodnet_amd import _lib, ops, weights
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(1, 12, 20, 64, generator=g).to(gpu)
+    wp = ops.pad_rows(weights.pack_conv_weight(torch.randn(64, 64, 1, 1, generator=g) / 8)).to(gpu)
+    y = torch.empty(1, 12, 20, 64, device=gpu)
+    d = ops.make_conv_desc(x, wp, 64, 1, 1, 1, 0, y, None, None, None, False, True)
+    tiles = ops.conv_cfg_tiles()
+    assert len(tiles) == 62
+    ran = 0
+    for cfg, (bm, bn) in enumerate(tiles):
+        if not _lib.lib().vfn_conv_cfg_modes(cfg) >> mode & 1:
+            with pytest.raises(RuntimeError):
+                ops.conv2d_launch(d, cfg, mode)
+        elif wp.shape[0] >= ((64 + bn - 1) // bn) * bn:
+            y.fill_(float('nan'))
+            ops.conv2d_launch(d, cfg, mode)
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(y).all()), cfg
+            ran += 1
+    assert ran == len(ops.conv_cfgs(mode)) == 27
 
 
 @pytest.mark.parametrize('shape', [(2, 12, 20, 64, 128, 3, 1), (1, 13, 19, 128, 64, 3, 2), (2, 9, 14, 256, 256, 1, 1), (1, 24, 40, 32, 32, 3, 1)])

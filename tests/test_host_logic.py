@@ -119,6 +119,11 @@ def test_persistent_choices_fall_back_for_descriptors_they_do_not_take():
     assert n >= 20, n
     for k, v in json.load(open(engine._TUNED_BF16_PATH)).items():
         assert v[0] < ops.PCONV_CFG0                                           # (the bf16 table: persistent ids for the Winograd GEMMs only)
+    # every tile configuration a shipped table names exists in that table's arithmetic mode (vfn_conv_cfg_modes)
+    for mode, path in enumerate(engine._TABLE_PATHS):
+        for k, v in json.load(open(path)).items():
+            for c in v[0::3]:                                                  # the choice and, where recorded, the fallback
+                assert c >= ops.WINO_GEMM_CFG0 or c in ops.conv_cfgs(mode), (path, k, v)
 
 
 def test_video_ds_and_palette(tmp_path):

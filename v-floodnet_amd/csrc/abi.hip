@@ -4,6 +4,7 @@
 // 3: vfn_memread_desc.wide (added at 2 without a bump), vfn_conv_cfg_info, vfn_sizeof_desc
 // 4: PNG / JPEG / segment-uncertainty / norm-refresh entry points (round 2)
 // 13: vfn_bankmatch_desc, vfn_bank_match_certified, vfn_bank_refresh_lp_keys
+// 15: vfn_conv_cfg_modes
 extern "C" int vfn_abi_version(void) { return VFN_ABI_VERSION; }
 
 // sizeof of every descriptor as THIS library was compiled: a binding whose struct layout drifted fails its

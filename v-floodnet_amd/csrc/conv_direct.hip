@@ -317,21 +317,16 @@ void conv_direct_kernel(const vfn_conv_desc p) {
     }
 }
 
-template <int TM, int TN, int GM, int GN, int WK, int OCC = 2>
+template <int TM, int TN, int GM, int GN, int WK, int OCC>
 int launch_direct(const vfn_conv_desc& p, hipStream_t s) {
     constexpr int NTL = GM * GN;
     constexpr int BM = 32 * TM * GM, BN = 32 * TN * GN;
     constexpr size_t lds_red = (size_t)(4 - NTL) * TM * TN * 16 * 64 * sizeof(float);
     constexpr size_t lds_c = (size_t)NTL * 32 * (32 * TN + 4) * sizeof(float);
     constexpr size_t lds = lds_red > lds_c ? lds_red : lds_c;
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_direct_kernel<TM, TN, GM, GN, WK, OCC, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_direct_kernel<TM, TN, GM, GN, WK, OCC, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    static const bool lds_ready = vfn_allow_lds(&conv_direct_kernel<TM, TN, GM, GN, WK, OCC, false>, lds) &&
+                                  vfn_allow_lds(&conv_direct_kernel<TM, TN, GM, GN, WK, OCC, true>, lds);
+    (void)lds_ready;
     const int m_tiles = cdiv(p.M, BM);
     const int n_tiles = cdiv(p.Cout, BN);
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
@@ -556,6 +551,8 @@ constexpr int kDirect[VFN_DIRECT_CFGS][5] = {
     // stream-K (GM = 0): {TM, TN, 0, waves per SIMD, 1}
     {2, 2, 0, 1, 1}, {2, 2, 0, 2, 1}, {1, 2, 0, 2, 1}, {2, 1, 0, 2, 1}, {1, 1, 0, 2, 1}, {1, 2, 0, 1, 1},
 };
+// OCC of conv_direct_kernel (workgroups per CU in its launch bounds): 1 for the wave tiles of eight 32x32 accumulators, else 2
+constexpr int direct_occ(const int* c) { return c[0] * c[1] > 4 ? 1 : 2; }
 
 }  // namespace
 
@@ -573,38 +570,16 @@ int vfn_conv_direct_name(int idx, char* buf, int n) {
     const int* c = kDirect[idx];
     // (the last template argument, ReLU on the input, is left open: "...<2, 2, 2" matches both instantiations as a prefix)
     if (c[2] == 0) snprintf(buf, n, "conv_streamk_kernel<%d, %d, %d", c[0], c[1], c[3] > 2 ? 2 : c[3]);
-    else snprintf(buf, n, "conv_direct_kernel<%d, %d, %d, %d, %d, %d", c[0], c[1], c[2], c[3], c[4], (c[0] * c[1] > 4) ? 1 : 2);
+    else snprintf(buf, n, "conv_direct_kernel<%d, %d, %d, %d, %d, %d", c[0], c[1], c[2], c[3], c[4], direct_occ(c));
     return VFN_OK;
 }
 
 int vfn_conv_direct_is_streamk(int idx) { return idx >= 0 && idx < VFN_DIRECT_CFGS && kDirect[idx][2] == 0; }
 
 int vfn_conv_direct_launch(const vfn_conv_desc& d, int idx, hipStream_t s) {
-    switch (idx) {
-        case 0: return launch_direct<2, 2, 2, 2, 1>(d, s);
-        case 1: return launch_direct<2, 2, 4, 1, 1>(d, s);
-        case 2: return launch_direct<2, 2, 2, 1, 2>(d, s);
-        case 3: return launch_direct<2, 2, 1, 2, 2>(d, s);
-        case 4: return launch_direct<2, 2, 1, 1, 4>(d, s);
-        case 5: return launch_direct<1, 2, 2, 2, 1>(d, s);
-        case 6: return launch_direct<1, 2, 4, 1, 1>(d, s);
-        case 7: return launch_direct<1, 2, 2, 1, 2>(d, s);
-        case 8: return launch_direct<1, 2, 1, 1, 4>(d, s);
-        case 9: return launch_direct<2, 1, 2, 2, 1>(d, s);
-        case 10: return launch_direct<2, 1, 4, 1, 1>(d, s);
-        case 11: return launch_direct<1, 1, 2, 2, 1>(d, s);
-        case 12: return launch_direct<1, 1, 4, 1, 1>(d, s);
-        case 13: return launch_direct<1, 1, 1, 1, 4>(d, s);
-        case 14: return launch_direct<2, 4, 2, 1, 2, 1>(d, s);
-        case 15: return launch_direct<2, 4, 2, 2, 1, 1>(d, s);
-        case 16: return launch_direct<4, 2, 2, 2, 1, 1>(d, s);
-        case 17: return launch_direct<2, 4, 1, 1, 4, 1>(d, s);
-        case 18: return launch_streamk<2, 2, 1>(d, s);
-        case 19: return launch_streamk<2, 2, 2>(d, s);
-        case 20: return launch_streamk<1, 2, 2>(d, s);
-        case 21: return launch_streamk<2, 1, 2>(d, s);
-        case 22: return launch_streamk<1, 1, 2>(d, s);
-        case 23: return launch_streamk<1, 2, 1>(d, s);
-    }
-    return VFN_ERR_ARG;
+    return vfn_dispatch<VFN_DIRECT_CFGS>(idx, [&](auto id) -> int {
+        constexpr const int* c = kDirect[decltype(id)::value];
+        if constexpr (c[2] == 0) return launch_streamk<c[0], c[1], c[3]>(d, s);
+        else return launch_direct<c[0], c[1], c[2], c[3], c[4], direct_occ(c)>(d, s);
+    });
 }

@@ -955,50 +955,102 @@ __global__ void splitk_reduce_kernel(const vfn_conv_desc p, int m_start) {
     }
 }
 
-template <int BM, int BN, int WM, int WN, int DMA = 0, int MODE = 0>     // DMA: 0 = register staged, 2 / 3 = LDS-DMA ring depth
+template <int BM, int BN, int WM, int WN, int DMA, int MODE>     // DMA: 0 = register staged, 2 / 3 = LDS-DMA ring depth
+constexpr auto tile_kernel() {
+    if constexpr (DMA != 0) return &conv_igemm_dma_kernel<BM, BN, WM, WN, DMA>;
+    else return &conv_igemm_kernel<BM, BN, WM, WN, MODE>;
+}
+
+template <int BM, int BN, int WM, int WN, int DMA, int MODE>
 int launch_cfg(const vfn_conv_desc& p, hipStream_t s) {
     constexpr int NT = WM * WN * 64;
-    const size_t lds = (DMA == 3 ? 3 : 2) * (size_t)(BM + BN) * BK * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        if constexpr (DMA != 0)
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_dma_kernel<BM, BN, WM, WN, DMA>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WM, WN, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    constexpr size_t lds = (DMA == 3 ? 3 : 2) * (size_t)(BM + BN) * BK * sizeof(float);
+    constexpr auto kern = tile_kernel<BM, BN, WM, WN, DMA, MODE>();
+    static const bool lds_ready = vfn_allow_lds(kern, lds);
+    (void)lds_ready;
     const int m_tiles = cdiv(p.M, BM);
     const int n_tiles = cdiv(p.Cout, BN);
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     const int tiles = m_tiles * n_tiles;
     if (ks > 1 && (p.split_from < 0 || p.split_from > tiles || p.split_from % n_tiles)) return VFN_ERR_ARG;
     const int grid = ks > 1 ? p.split_from + (tiles - p.split_from) * ks : tiles;
-    if constexpr (DMA != 0) hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WM, WN, DMA>), dim3(grid), dim3(NT), lds, s, p);
-    else hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, MODE>), dim3(grid), dim3(NT), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, p);
     if (ks > 1 && p.split_from < tiles && !p.tile_counters) {
         vfn_conv_splitk_reduce(p, (p.split_from / n_tiles) * BM, s);
     }
     return vfn_check_launch();
 }
 
-template <int BM, int BN, int WM, int WN, int WK, int PD = 3, int TPB = 1, int MODE = 0>
+template <int BM, int BN, int WM, int WN, int WK, int PD, int TPB, int MODE>
 int launch_wk(const vfn_conv_desc& p, hipStream_t s) {
     constexpr int NT = WM * WN * WK * 64;
     constexpr size_t lds = (size_t)WK * 2 * TPB * (BM + BN) * BK * sizeof(float);
     static_assert((size_t)(WK - 1) * BM * BN * sizeof(float) <= lds, "reduce buffer does not fit the staging LDS");
     static_assert(lds <= 160 * 1024 && NT <= 1024, "workgroup too large");
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_wk_kernel<BM, BN, WM, WN, WK, PD, TPB, MODE>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    static const bool lds_ready = vfn_allow_lds(&conv_igemm_wk_kernel<BM, BN, WM, WN, WK, PD, TPB, MODE>, lds);
+    (void)lds_ready;
     if (p.ksplit > 1) return VFN_ERR_ARG;                  // one kind of split at a time
     const int tiles = cdiv(p.M, BM) * cdiv(p.Cout, BN);
     hipLaunchKernelGGL((conv_igemm_wk_kernel<BM, BN, WM, WN, WK, PD, TPB, MODE>), dim3(tiles), dim3(NT), lds, s, p);
     return vfn_check_launch();
+}
+
+// The LDS-tiled configurations, ids 0 .. 37, stated once: the queries, the mode check and the launch below all read this table.
+// The ids are persisted in the tuned tables (tuned_gfx950*.json), so rows are appended and never renumbered.
+//   bm x bn   workgroup tile;  wm x wn  wave grid
+//   dma       0 = register-staged (conv_igemm_kernel), 2 = LDS-DMA ring (conv_igemm_dma_kernel; f32 only: the DMA cannot convert)
+//   wk        K groups per workgroup (> 1: split-K inside the workgroup; ksplit must be <= 1)
+//   pd, tpb   K tiles prefetched in registers / multiplied between two barriers; pd > 1 is conv_igemm_wk_kernel
+//   modes     arithmetic modes that accept the row: bit 0 f32, bit 1 bf16, bit 2 bf16x3
+struct conv_cfg { int bm, bn, wm, wn, dma, wk, pd, tpb, modes; };
+constexpr int F32 = 1, ANY = 7;
+constexpr conv_cfg kCfg[VFN_DIRECT_CFG0] = {
+    {128, 128, 2, 2, 0, 1, 1, 1, ANY}, {128, 64, 2, 2, 0, 1, 1, 1, ANY}, {64, 128, 2, 2, 0, 1, 1, 1, ANY}, {64, 64, 2, 2, 0, 1, 1, 1, ANY},
+    {32, 64, 1, 2, 0, 1, 1, 1, ANY}, {64, 32, 2, 1, 0, 1, 1, 1, ANY}, {128, 32, 4, 1, 0, 1, 1, 1, ANY}, {256, 128, 4, 2, 0, 1, 1, 1, ANY},
+    // 8..10: the tiles of 0 / 0 / 2 with twice the waves (smaller per-wave tiles, 4 waves per SIMD at 2 blocks/CU)
+    {128, 128, 2, 4, 0, 1, 1, 1, ANY}, {128, 128, 4, 2, 0, 1, 1, 1, ANY}, {64, 128, 2, 4, 0, 1, 1, 1, ANY},
+    // 11..16: LDS-DMA staging variants of 8 / 10 / 3 / 7 / 6 / 2
+    {128, 128, 2, 4, 2, 1, 1, 1, F32}, {64, 128, 2, 4, 2, 1, 1, 1, F32}, {64, 64, 2, 2, 2, 1, 1, 1, F32}, {256, 128, 4, 2, 2, 1, 1, 1, F32},
+    {128, 32, 4, 1, 2, 1, 1, 1, F32}, {64, 128, 2, 2, 2, 1, 1, 1, F32},
+    // 17..19: 256-filter-wide tiles (input tile read once for all 256 filters): 128x256 and 64x256, 8 waves
+    {128, 256, 2, 4, 0, 1, 1, 1, ANY}, {128, 256, 2, 4, 2, 1, 1, 1, F32}, {64, 256, 2, 4, 0, 1, 1, 1, ANY},
+    // 20..25: 32-row tiles for the 1/16-resolution layers (M = 1620: 51 x 32 rows instead of 26 x 64), single-wave 32x32 tiles (most
+    // workgroups for the smallest layers), and 8-wave variants of 128x64 / 256x64 -- the tall tiles for the 64-filter layers: fewer
+    // operand bytes per FLOP from L2 (the reduced-precision K loop is L2 -> LDS bound)
+    {32, 128, 1, 4, 0, 1, 1, 1, F32}, {32, 32, 1, 1, 0, 1, 1, 1, F32}, {128, 64, 4, 2, 0, 1, 1, 1, ANY}, {256, 64, 4, 2, 0, 1, 1, 1, ANY},
+    {32, 64, 1, 1, 0, 1, 1, 1, F32}, {64, 64, 1, 2, 0, 1, 1, 1, F32},
+    // 26..31: in-workgroup split-K with a 3-tile register prefetch
+    {32, 64, 1, 2, 0, 4, 3, 1, ANY}, {64, 64, 2, 2, 0, 2, 3, 1, ANY}, {32, 64, 1, 2, 0, 2, 3, 1, ANY}, {64, 64, 2, 2, 0, 4, 3, 1, ANY},
+    {32, 32, 1, 1, 0, 4, 3, 1, ANY}, {32, 128, 1, 4, 0, 2, 3, 1, ANY},
+    // 32..37: two K tiles per barrier with a 4-tile register prefetch, with and without the in-workgroup split
+    {32, 64, 1, 2, 0, 2, 4, 2, ANY}, {64, 64, 2, 2, 0, 2, 4, 2, ANY}, {32, 64, 1, 2, 0, 1, 4, 2, ANY}, {64, 64, 2, 2, 0, 1, 4, 2, ANY},
+    {64, 128, 2, 4, 0, 1, 4, 2, ANY}, {32, 128, 1, 4, 0, 1, 4, 2, ANY},
+};
+
+// cfg -> the instantiation its row names; a row without MODE's bit is not instantiated for MODE
+template <int MODE>
+int launch_tiled(const vfn_conv_desc& d, int cfg, hipStream_t s) {
+    return vfn_dispatch<VFN_DIRECT_CFG0>(cfg, [&](auto id) -> int {
+        constexpr conv_cfg c = kCfg[decltype(id)::value];
+        if constexpr (!(c.modes >> MODE & 1)) return VFN_ERR_ARG;
+        else if constexpr (c.pd > 1) return launch_wk<c.bm, c.bn, c.wm, c.wn, c.wk, c.pd, c.tpb, MODE>(d, s);
+        else return launch_cfg<c.bm, c.bn, c.wm, c.wn, c.dma, MODE>(d, s);
+    });
+}
+
+// What the three entry points refuse alike.  kt: channels per K tile of the mode; the tile of cfg comes back in bm / bn.
+int check_desc(const vfn_conv_desc* d, int cfg, int kt, int* bm, int* bn) {
+    if (!d || !d->in || !d->w) return VFN_ERR_ARG;
+    if (d->Cin % kt != 0 || d->in_ld % 4 != 0 || d->M <= 0) return VFN_ERR_ARG;
+    if (vfn_conv_cfg_tile(cfg, bm, bn) != VFN_OK) return VFN_ERR_ARG;
+    if (d->cout_pad < cdiv(d->Cout, *bn) * *bn) return VFN_ERR_ARG;
+    if (d->w_batch_rows < 0 || (d->w_batch_rows > 0 && (d->w_batch_rows % *bm || d->KH != 1 || d->KW != 1))) return VFN_ERR_ARG;
+    if (d->ksplit > 1) {
+        const int nk_all = d->KH * d->KW * (d->Cin / kt);
+        if (!d->partial || d->Cout % 4 || d->out_ld % 4 || (d->res && d->res_ld % 4)) return VFN_ERR_ARG;
+        if (cdiv(nk_all, d->ksplit) * (d->ksplit - 1) >= nk_all) return VFN_ERR_ARG;   // every split non-empty
+    }
+    return VFN_OK;
 }
 
 }  // namespace
@@ -1009,44 +1061,27 @@ void vfn_conv_splitk_reduce(const vfn_conv_desc& p, int m_start, hipStream_t s) 
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p, m_start);
 }
 
+// Queries over all configurations: kCfg rows, then the wave-autonomous and stream-K kernels of conv_direct.hip (f32 only)
 constexpr int kCfgCount = VFN_DIRECT_CFG0 + VFN_DIRECT_CFGS;
 extern "C" int vfn_conv_cfg_count(void) { return kCfgCount; }
 
-// K groups per workgroup of a tile configuration (1 = none): configurations 26.. split K inside the workgroup
 extern "C" int vfn_conv_cfg_wk(int cfg) {
-    static const int wk[12] = {4, 2, 2, 4, 4, 2, 2, 2, 1, 1, 1, 1};
     if (cfg < 0 || cfg >= kCfgCount) return 0;
     if (cfg >= VFN_DIRECT_CFG0) { int w = 0; vfn_conv_direct_info(cfg - VFN_DIRECT_CFG0, nullptr, nullptr, &w); return w; }
-    return cfg < 26 ? 1 : wk[cfg - 26];
+    return kCfg[cfg].wk;
 }
 
-// K tiles between two workgroup barriers (1 for all but configurations 32..37, which run 2 with a 4-tile register prefetch)
 extern "C" int vfn_conv_cfg_tpb(int cfg) {
     if (cfg < 0 || cfg >= kCfgCount) return 0;
-    return (cfg < 32 || cfg >= VFN_DIRECT_CFG0) ? 1 : 2;
+    return cfg >= VFN_DIRECT_CFG0 ? 1 : kCfg[cfg].tpb;
+}
+
+extern "C" int vfn_conv_cfg_modes(int cfg) {
+    if (cfg < 0 || cfg >= kCfgCount) return 0;
+    return cfg >= VFN_DIRECT_CFG0 ? F32 : kCfg[cfg].modes;
 }
 
 extern "C" int vfn_conv_cfg_info(int cfg, int* bm, int* bn, int* wm, int* wn, int* dma) {
-    // 8..10: same tiles as 0 / 0 / 2 with twice the waves (smaller per-wave tiles, 4 waves per SIMD at 2 blocks/CU)
-    // 11..16: LDS-DMA staging variants of 8 / 10 / 3 / 7 / 6 / 2
-    // 17..19: 256-filter-wide tiles (input tile read once for all 256 filters): 128x256 and 64x256, 8 waves
-    // (must match the switch of vfn_conv2d_nhwc_f32 below)
-    // 20..25 (f32 only): 32-row tiles for the 1/16-resolution layers (M = 1620: 51 x 32 rows instead of 26 x 64),
-    // single-wave 32x32 tiles (most workgroups for the smallest layers), and 8-wave variants of 128x64 / 256x64
-    // 26..37 (any arithmetic mode; ksplit must be 1): in-workgroup split-K (vfn_conv_cfg_wk K groups of the WM x WN waves) and,
-    // from 32 on, two K tiles per barrier (vfn_conv_cfg_tpb)
-    static const int t[38][5] = {{128, 128, 2, 2, 0}, {128, 64, 2, 2, 0}, {64, 128, 2, 2, 0}, {64, 64, 2, 2, 0}, {32, 64, 1, 2, 0},
-                                 {64, 32, 2, 1, 0}, {128, 32, 4, 1, 0}, {256, 128, 4, 2, 0},
-                                 {128, 128, 2, 4, 0}, {128, 128, 4, 2, 0}, {64, 128, 2, 4, 0},
-                                 {128, 128, 2, 4, 2}, {64, 128, 2, 4, 2}, {64, 64, 2, 2, 2}, {256, 128, 4, 2, 2}, {128, 32, 4, 1, 2},
-                                 {64, 128, 2, 2, 2},
-                                 {128, 256, 2, 4, 0}, {128, 256, 2, 4, 2}, {64, 256, 2, 4, 0},
-                                 {32, 128, 1, 4, 0}, {32, 32, 1, 1, 0}, {128, 64, 4, 2, 0}, {256, 64, 4, 2, 0}, {32, 64, 1, 1, 0},
-                                 {64, 64, 1, 2, 0},
-                                 {32, 64, 1, 2, 0}, {64, 64, 2, 2, 0}, {32, 64, 1, 2, 0}, {64, 64, 2, 2, 0}, {32, 32, 1, 1, 0},
-                                 {32, 128, 1, 4, 0},
-                                 {32, 64, 1, 2, 0}, {64, 64, 2, 2, 0}, {32, 64, 1, 2, 0}, {64, 64, 2, 2, 0}, {64, 128, 2, 4, 0},
-                                 {32, 128, 1, 4, 0}};
     if (cfg >= VFN_DIRECT_CFG0 && cfg < kCfgCount) {
         // wave-autonomous kernels (conv_direct.hip): 4 waves; reported as wm = wn = 0, dma = 9
         if (wm) *wm = 0;
@@ -1054,12 +1089,12 @@ extern "C" int vfn_conv_cfg_info(int cfg, int* bm, int* bn, int* wm, int* wn, in
         if (dma) *dma = 9;
         return vfn_conv_direct_info(cfg - VFN_DIRECT_CFG0, bm, bn, nullptr);
     }
-    if (cfg < 0 || cfg >= 38) return VFN_ERR_ARG;
-    if (bm) *bm = t[cfg][0];
-    if (bn) *bn = t[cfg][1];
-    if (wm) *wm = t[cfg][2];
-    if (wn) *wn = t[cfg][3];
-    if (dma) *dma = t[cfg][4];
+    if (cfg < 0 || cfg >= VFN_DIRECT_CFG0) return VFN_ERR_ARG;
+    if (bm) *bm = kCfg[cfg].bm;
+    if (bn) *bn = kCfg[cfg].bn;
+    if (wm) *wm = kCfg[cfg].wm;
+    if (wn) *wn = kCfg[cfg].wn;
+    if (dma) *dma = kCfg[cfg].dma;
     return VFN_OK;
 }
 
@@ -1076,161 +1111,45 @@ extern "C" int vfn_conv_cfg_name(int cfg, char* buf, int n) {
 
 extern "C" int vfn_conv_cfg_tile(int cfg, int* bm, int* bn) { return vfn_conv_cfg_info(cfg, bm, bn, nullptr, nullptr, nullptr); }
 
-// configurations 26..37 (in-workgroup split-K / deep prefetch / two tiles per barrier) in any arithmetic mode
-template <int MODE>
-int launch_wk_cfg(const vfn_conv_desc& d, int cfg, hipStream_t s) {
-    switch (cfg) {
-        case 26: return launch_wk<32, 64, 1, 2, 4, 3, 1, MODE>(d, s);
-        case 27: return launch_wk<64, 64, 2, 2, 2, 3, 1, MODE>(d, s);
-        case 28: return launch_wk<32, 64, 1, 2, 2, 3, 1, MODE>(d, s);
-        case 29: return launch_wk<64, 64, 2, 2, 4, 3, 1, MODE>(d, s);
-        case 30: return launch_wk<32, 32, 1, 1, 4, 3, 1, MODE>(d, s);
-        case 31: return launch_wk<32, 128, 1, 4, 2, 3, 1, MODE>(d, s);
-        case 32: return launch_wk<32, 64, 1, 2, 2, 4, 2, MODE>(d, s);
-        case 33: return launch_wk<64, 64, 2, 2, 2, 4, 2, MODE>(d, s);
-        case 34: return launch_wk<32, 64, 1, 2, 1, 4, 2, MODE>(d, s);
-        case 35: return launch_wk<64, 64, 2, 2, 1, 4, 2, MODE>(d, s);
-        case 36: return launch_wk<64, 128, 2, 4, 1, 4, 2, MODE>(d, s);
-        case 37: return launch_wk<32, 128, 1, 4, 1, 4, 2, MODE>(d, s);
-    }
-    return VFN_ERR_ARG;
-}
-
 extern "C" int vfn_conv2d_nhwc_f32(const vfn_conv_desc* d, int cfg, void* stream) {
-    if (!d || !d->in || !d->w || !d->out || d->in_lp || d->out_lp) return VFN_ERR_ARG;
-    if (d->Cin % BK != 0 || d->in_ld % 4 != 0 || d->M <= 0) return VFN_ERR_ARG;
     int bm, bn;
-    if (vfn_conv_cfg_tile(cfg, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
-    if (d->cout_pad < cdiv(d->Cout, bn) * bn) return VFN_ERR_ARG;
-    if (d->w_batch_rows < 0 || (d->w_batch_rows > 0 && (d->w_batch_rows % bm || d->KH != 1 || d->KW != 1))) return VFN_ERR_ARG;
-    if (d->ksplit > 1) {
-        const int nk_all = d->KH * d->KW * (d->Cin / BK);
-        if (!d->partial || d->Cout % 4 || d->out_ld % 4 || (d->res && d->res_ld % 4) || (d->mask && d->mask_ld % 4)) return VFN_ERR_ARG;
-        if (d->tile_counters && d->Cout % bn) return VFN_ERR_ARG;      // in-launch finish works on whole filter tiles
-        if (cdiv(nk_all, d->ksplit) * (d->ksplit - 1) >= nk_all) return VFN_ERR_ARG;   // every split non-empty
-        if (d->tile_counters) {
-            // the in-launch finish addresses the partial slabs through ONE buffer resource with 32-bit byte offsets
-            // (off + slice * slab): refuse what would wrap instead of dropping stores / loading zeros silently
-            const int nt = cdiv(d->Cout, bn);
-            if (d->split_from < 0 || d->split_from % nt) return VFN_ERR_ARG;
-            const long long m_start = (long long)(d->split_from / nt) * bm;
-            if ((long long)d->ksplit * ((long long)d->M - m_start) * d->Cout * (long long)sizeof(float) >= 0x7fffff00LL) return VFN_ERR_ARG;
-        }
+    if (check_desc(d, cfg, BK, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
+    if (!d->out || d->in_lp || d->out_lp) return VFN_ERR_ARG;
+    if (d->ksplit > 1 && d->mask && d->mask_ld % 4) return VFN_ERR_ARG;
+    if (d->ksplit > 1 && d->tile_counters) {
+        // the in-launch finish works on whole filter tiles and addresses the partial slabs through ONE buffer resource with 32-bit
+        // byte offsets (off + slice * slab): refuse what would wrap instead of dropping stores / loading zeros silently
+        const int nt = cdiv(d->Cout, bn);
+        if (d->Cout % bn || d->split_from < 0 || d->split_from % nt) return VFN_ERR_ARG;
+        const long long m_start = (long long)(d->split_from / nt) * bm;
+        if ((long long)d->ksplit * ((long long)d->M - m_start) * d->Cout * (long long)sizeof(float) >= 0x7fffff00LL) return VFN_ERR_ARG;
     }
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_cfg<128, 128, 2, 2>(*d, s);
-        case 1: return launch_cfg<128, 64, 2, 2>(*d, s);
-        case 2: return launch_cfg<64, 128, 2, 2>(*d, s);
-        case 3: return launch_cfg<64, 64, 2, 2>(*d, s);
-        case 4: return launch_cfg<32, 64, 1, 2>(*d, s);
-        case 5: return launch_cfg<64, 32, 2, 1>(*d, s);
-        case 6: return launch_cfg<128, 32, 4, 1>(*d, s);
-        case 7: return launch_cfg<256, 128, 4, 2>(*d, s);
-        case 8: return launch_cfg<128, 128, 2, 4>(*d, s);
-        case 9: return launch_cfg<128, 128, 4, 2>(*d, s);
-        case 10: return launch_cfg<64, 128, 2, 4>(*d, s);
-        case 11: return launch_cfg<128, 128, 2, 4, 2>(*d, s);
-        case 12: return launch_cfg<64, 128, 2, 4, 2>(*d, s);
-        case 13: return launch_cfg<64, 64, 2, 2, 2>(*d, s);
-        case 14: return launch_cfg<256, 128, 4, 2, 2>(*d, s);
-        case 15: return launch_cfg<128, 32, 4, 1, 2>(*d, s);
-        case 16: return launch_cfg<64, 128, 2, 2, 2>(*d, s);
-        case 17: return launch_cfg<128, 256, 2, 4>(*d, s);
-        case 18: return launch_cfg<128, 256, 2, 4, 2>(*d, s);
-        case 19: return launch_cfg<64, 256, 2, 4>(*d, s);
-        case 20: return launch_cfg<32, 128, 1, 4>(*d, s);
-        case 21: return launch_cfg<32, 32, 1, 1>(*d, s);
-        case 22: return launch_cfg<128, 64, 4, 2>(*d, s);
-        case 23: return launch_cfg<256, 64, 4, 2>(*d, s);
-        case 24: return launch_cfg<32, 64, 1, 1>(*d, s);
-        case 25: return launch_cfg<64, 64, 1, 2>(*d, s);
-        default:
-            if (cfg >= 26 && cfg <= 37) return launch_wk_cfg<0>(*d, cfg, s);
-            if (cfg >= VFN_DIRECT_CFG0 && cfg < kCfgCount) return vfn_conv_direct_launch(*d, cfg - VFN_DIRECT_CFG0, s);
-    }
-    return VFN_ERR_ARG;
+    if (cfg >= VFN_DIRECT_CFG0) return vfn_conv_direct_launch(*d, cfg - VFN_DIRECT_CFG0, (hipStream_t)stream);
+    return launch_tiled<0>(*d, cfg, (hipStream_t)stream);
 }
 
-// Same convolution with bf16 operands (rounded to nearest-even as they are staged; f32 accumulate, f32
-// tensors in HBM): BASELINE configs C3 / C5.  Register-staged tile configurations only (LDS-DMA cannot convert).
+// Same convolution with bf16 operands (rounded to nearest-even as they are staged; f32 accumulate, f32 tensors in HBM): BASELINE
+// configs C3 / C5.  K tiles of 64 channels.  Batched filters (the transform-domain GEMMs of Winograd layers in this mode) take the
+// f32 banks and convert them as staged.
 extern "C" int vfn_conv2d_nhwc_bf16(const vfn_conv_desc* d, int cfg, void* stream) {
-    if (!d || !d->in || !d->w || !d->out || d->in_lp || d->out_lp) return VFN_ERR_ARG;
-    // (batched filters -- the transform-domain GEMMs of Winograd layers in this mode, round 5 -- take the f32 banks and convert them as staged)
-    if (d->w_batch_rows < 0 || (d->w_batch_rows > 0 && (d->w_packed || d->KH != 1 || d->KW != 1))) return VFN_ERR_ARG;
-    if (d->Cin % 64 != 0 || d->in_ld % 4 != 0 || d->M <= 0) return VFN_ERR_ARG;
     int bm, bn;
-    if (vfn_conv_cfg_tile(cfg, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
-    if (d->cout_pad < cdiv(d->Cout, bn) * bn) return VFN_ERR_ARG;
-    if (d->w_batch_rows > 0 && d->w_batch_rows % bm) return VFN_ERR_ARG;
-    if (d->tile_counters) return VFN_ERR_ARG;
-    if (d->ksplit > 1) {
-        const int nk_all = d->KH * d->KW * (d->Cin / 64);
-        if (!d->partial || d->Cout % 4 || d->out_ld % 4 || (d->res && d->res_ld % 4)) return VFN_ERR_ARG;
-        if (cdiv(nk_all, d->ksplit) * (d->ksplit - 1) >= nk_all) return VFN_ERR_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_cfg<128, 128, 2, 2, 0, 1>(*d, s);
-        case 1: return launch_cfg<128, 64, 2, 2, 0, 1>(*d, s);
-        case 2: return launch_cfg<64, 128, 2, 2, 0, 1>(*d, s);
-        case 3: return launch_cfg<64, 64, 2, 2, 0, 1>(*d, s);
-        case 4: return launch_cfg<32, 64, 1, 2, 0, 1>(*d, s);
-        case 5: return launch_cfg<64, 32, 2, 1, 0, 1>(*d, s);
-        case 6: return launch_cfg<128, 32, 4, 1, 0, 1>(*d, s);
-        case 7: return launch_cfg<256, 128, 4, 2, 0, 1>(*d, s);
-        case 8: return launch_cfg<128, 128, 2, 4, 0, 1>(*d, s);
-        case 9: return launch_cfg<128, 128, 4, 2, 0, 1>(*d, s);
-        case 10: return launch_cfg<64, 128, 2, 4, 0, 1>(*d, s);
-        case 17: return launch_cfg<128, 256, 2, 4, 0, 1>(*d, s);
-        case 19: return launch_cfg<64, 256, 2, 4, 0, 1>(*d, s);
-        case 22: return launch_cfg<128, 64, 4, 2, 0, 1>(*d, s);
-        case 23: return launch_cfg<256, 64, 4, 2, 0, 1>(*d, s);
-        default: if (cfg >= 26 && cfg <= 37) return launch_wk_cfg<1>(*d, cfg, s);
-    }
-    return VFN_ERR_ARG;
+    if (check_desc(d, cfg, 64, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
+    if (!d->out || d->in_lp || d->out_lp || d->tile_counters || (d->w_batch_rows > 0 && d->w_packed)) return VFN_ERR_ARG;
+    return launch_tiled<1>(*d, cfg, (hipStream_t)stream);
 }
 
 // "bf16x3": operands split into hi + lo bf16 halves as they are staged (16 significant bits), three bf16 MFMAs per
 // product (hi*hi + hi*lo + lo*hi), f32 accumulate: relative error ~2^-16 per product, against 2^-9 for plain bf16
-// and 2^-24 for f32.  Same tile configurations and K tiling (32 channels) as the f32 kernel's register-staged ones.
+// and 2^-24 for f32.  K tiling (32 channels) as the f32 kernel.
 extern "C" int vfn_conv2d_nhwc_bf16x3(const vfn_conv_desc* d, int cfg, void* stream) {
-    if (!d || !d->in || !d->w || (!d->out && !d->out_lp)) return VFN_ERR_ARG;
-    if (d->w_batch_rows < 0 || (d->w_batch_rows > 0 && (d->w_packed || d->in_lp || d->out_lp || d->KH != 1 || d->KW != 1))) return VFN_ERR_ARG;
+    int bm, bn;
+    if (check_desc(d, cfg, BK, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
+    if ((!d->out && !d->out_lp) || d->tile_counters) return VFN_ERR_ARG;
+    if (d->w_batch_rows > 0 && (d->w_packed || d->in_lp || d->out_lp)) return VFN_ERR_ARG;
     if (d->in_lp && (d->relu_in || d->in_ld % 32)) return VFN_ERR_ARG;            // ReLU belongs to the image's producer
     // the image is written by the 16-byte epilogue only (4 channels per lane): shapes that fall back to the dword form are refused
-    if (d->out_lp && (d->Cout % 32 || d->out_ld % 32 || (d->res && d->res_ld % 4) || d->tile_counters)) return VFN_ERR_ARG;
-    if (d->Cin % BK != 0 || d->in_ld % 4 != 0 || d->M <= 0) return VFN_ERR_ARG;
-    int bm, bn;
-    if (vfn_conv_cfg_tile(cfg, &bm, &bn) != VFN_OK) return VFN_ERR_ARG;
-    if (d->cout_pad < cdiv(d->Cout, bn) * bn) return VFN_ERR_ARG;
-    if (d->w_batch_rows > 0 && d->w_batch_rows % bm) return VFN_ERR_ARG;
-    if (d->tile_counters) return VFN_ERR_ARG;
-    if (d->ksplit > 1) {
-        const int nk_all = d->KH * d->KW * (d->Cin / BK);
-        if (!d->partial || d->Cout % 4 || d->out_ld % 4 || (d->res && d->res_ld % 4)) return VFN_ERR_ARG;
-        if (cdiv(nk_all, d->ksplit) * (d->ksplit - 1) >= nk_all) return VFN_ERR_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_cfg<128, 128, 2, 2, 0, 2>(*d, s);
-        case 1: return launch_cfg<128, 64, 2, 2, 0, 2>(*d, s);
-        case 2: return launch_cfg<64, 128, 2, 2, 0, 2>(*d, s);
-        case 3: return launch_cfg<64, 64, 2, 2, 0, 2>(*d, s);
-        case 4: return launch_cfg<32, 64, 1, 2, 0, 2>(*d, s);
-        case 5: return launch_cfg<64, 32, 2, 1, 0, 2>(*d, s);
-        case 6: return launch_cfg<128, 32, 4, 1, 0, 2>(*d, s);
-        case 7: return launch_cfg<256, 128, 4, 2, 0, 2>(*d, s);
-        case 8: return launch_cfg<128, 128, 2, 4, 0, 2>(*d, s);
-        case 9: return launch_cfg<128, 128, 4, 2, 0, 2>(*d, s);
-        case 10: return launch_cfg<64, 128, 2, 4, 0, 2>(*d, s);
-        case 17: return launch_cfg<128, 256, 2, 4, 0, 2>(*d, s);
-        case 19: return launch_cfg<64, 256, 2, 4, 0, 2>(*d, s);
-        case 22: return launch_cfg<128, 64, 4, 2, 0, 2>(*d, s);      // tall tiles for the 64-filter layers: fewer operand bytes per
-        case 23: return launch_cfg<256, 64, 4, 2, 0, 2>(*d, s);      // FLOP from L2 (the reduced-precision K loop is L2 -> LDS bound)
-        default: if (cfg >= 26 && cfg <= 37) return launch_wk_cfg<2>(*d, cfg, s);
-    }
-    return VFN_ERR_ARG;
+    if (d->out_lp && (d->Cout % 32 || d->out_ld % 32 || (d->res && d->res_ld % 4))) return VFN_ERR_ARG;
+    return launch_tiled<2>(*d, cfg, (hipStream_t)stream);
 }
 
 #ifdef VFN_CENSUS

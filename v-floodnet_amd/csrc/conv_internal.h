@@ -1,7 +1,27 @@
 // Internal seams between the convolution translation units (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <utility>
 #include "../../include/vfn_hip.h"
+
+// Runtime index -> compile-time index: returns f(std::integral_constant<int, I>()) for the I in [0, N) equal to i, VFN_ERR_ARG when
+// there is none.  Every convolution launcher turns a configuration id into the instantiation its table row names through this.
+template <class F, int... I>
+int vfn_dispatch_seq(int i, F&& f, std::integer_sequence<int, I...>) {
+    int r = VFN_ERR_ARG;
+    (void)((i == I && (r = f(std::integral_constant<int, I>()), true)) || ...);
+    return r;
+}
+template <int N, class F>
+int vfn_dispatch(int i, F&& f) { return vfn_dispatch_seq(i, f, std::make_integer_sequence<int, N>()); }
+
+// Raises a kernel's dynamic-LDS limit where it needs more than the default 64 KB.  The launchers call it from a function-local static
+// initialiser: once per instantiation, and safe when two host threads reach a launcher together.
+template <typename K>
+bool vfn_allow_lds(K kern, size_t bytes) {
+    if (bytes > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return true;
+}
 
 // tile configurations VFN_DIRECT_CFG0 .. VFN_DIRECT_CFG0 + VFN_DIRECT_CFGS - 1 of vfn_conv2d_nhwc_f32 are the
 // wave-autonomous kernels of conv_direct.hip (f32 only)

@@ -14,6 +14,7 @@
 // Both transforms are HBM-bound: a thread owns 4 channels of one tile, so every load / store of a wave is a contiguous
 // 256-byte to 1-KB row; V and M cost 36/16 of the tensor each way (119 MB each for 2 x 120 x 216 x 256).
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/vfn_hip.h"
 
 namespace {
@@ -537,14 +538,11 @@ void wino_gemm_kernel(const wino_gemm_args p) {
     }
 }
 
-template <int BM, int BN, int WM, int WN, int PD, bool CONV = false, bool LP = false>
+template <int BM, int BN, int WM, int WN, int PD, bool CONV, bool LP>
 int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s) {
     constexpr size_t lds = 2 * (size_t)(BM + BN) * 32 * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    static const bool lds_ready = vfn_allow_lds(&wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>, lds);
+    (void)lds_ready;
     wino_gemm_args p = a;
     p.mtiles = (a.rows_pad + BM - 1) / BM;
     p.ntiles = (a.Cout + BN - 1) / BN;
@@ -554,6 +552,20 @@ int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s) {
     grid = (grid + 7) / 8 * 8;                              // (the kernel deals units to blockIdx & 7 = XCD, blockIdx >> 3 = slot)
     hipLaunchKernelGGL((wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>), dim3(grid), dim3(WM * WN * 64), lds, s, p);
     return vfn_check_launch();
+}
+
+// Configurations of the persistent GEMM: cfg & 3 picks the tile {BM, BN, WM, WN}, cfg >> 2 the prefetch (operand tiles requested
+// PD = 1 or 2 K tiles ahead).  CONV: the 1x1 convolution's addressing and epilogue; LP: bf16 operands.
+constexpr int kWinoTile[4][4] = {{128, 128, 4, 2}, {64, 128, 2, 4}, {128, 64, 4, 2}, {64, 64, 2, 2}};
+constexpr int kWinoCfgs = 8;
+
+template <bool CONV, bool LP>
+int launch_wino_cfg(const wino_gemm_args& a, int cfg, int wgs, hipStream_t s) {
+    return vfn_dispatch<kWinoCfgs>(cfg, [&](auto id) -> int {
+        constexpr int c = decltype(id)::value;
+        constexpr const int* t = kWinoTile[c & 3];
+        return launch_wino_gemm<t[0], t[1], t[2], t[3], 1 + (c >> 2), CONV, LP>(a, wgs, s);
+    });
 }
 
 // the transforms address activations through buffer resources with 32-bit byte offsets: every tensor must stay below 2 GiB
@@ -627,24 +639,12 @@ extern "C" int vfn_winograd_dw_f32(const float* dU, int Cout, int Cin, const flo
 // filter count, C a multiple of 32; every operand below 2 GiB (32-bit buffer offsets)
 extern "C" int vfn_winograd_gemm_f32(const float* V, const float* U, float* Mb, int comps, int rows_pad, int C, int Cout, int cout_pad, int cfg,
                                      int wgs, void* stream) {
-    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 32 || C % 32 || Cout < 1 || cout_pad < Cout || cfg < 0 || cfg > 7) return VFN_ERR_ARG;
-    static const int bm[4] = {128, 64, 128, 64}, bn[4] = {128, 128, 64, 64};
-    const int tc = cfg & 3;
-    if (rows_pad % bm[tc] || cout_pad < (Cout + bn[tc] - 1) / bn[tc] * bn[tc]) return VFN_ERR_ARG;
+    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 32 || C % 32 || Cout < 1 || cout_pad < Cout || cfg < 0 || cfg >= kWinoCfgs) return VFN_ERR_ARG;
+    const int bm = kWinoTile[cfg & 3][0], bn = kWinoTile[cfg & 3][1];
+    if (rows_pad % bm || cout_pad < (Cout + bn - 1) / bn * bn) return VFN_ERR_ARG;
     if ((long long)comps * rows_pad * C * 4 >= 0x7fffff00LL || (long long)comps * cout_pad * C * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
     wino_gemm_args a{V, U, Mb, comps, rows_pad, C, Cout, cout_pad, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_wino_gemm<128, 128, 4, 2, 1>(a, wgs, s);
-        case 1: return launch_wino_gemm<64, 128, 2, 4, 1>(a, wgs, s);
-        case 2: return launch_wino_gemm<128, 64, 4, 2, 1>(a, wgs, s);
-        case 3: return launch_wino_gemm<64, 64, 2, 2, 1>(a, wgs, s);
-        case 4: return launch_wino_gemm<128, 128, 4, 2, 2>(a, wgs, s);
-        case 5: return launch_wino_gemm<64, 128, 2, 4, 2>(a, wgs, s);
-        case 6: return launch_wino_gemm<128, 64, 4, 2, 2>(a, wgs, s);
-        case 7: return launch_wino_gemm<64, 64, 2, 2, 2>(a, wgs, s);
-    }
-    return VFN_ERR_ARG;
+    return launch_wino_cfg<false, false>(a, cfg, wgs, (hipStream_t)stream);
 }
 
 // (ABI 12) a 1x1 / stride-1 convolution (+ eval BatchNorm / bias, residual, ReLU: the trunk's conv1 / conv3 / downsample, AFB_URR.py:59-61,
@@ -655,28 +655,17 @@ extern "C" int vfn_winograd_gemm_f32(const float* V, const float* U, float* Mb, 
 // order as vfn_conv2d_nhwc_f32 without split-K.  cfg / wgs as vfn_winograd_gemm_f32.  Refuses what it does not implement (taps, strides,
 // masks, operand images, split-K) with VFN_ERR_ARG.
 extern "C" int vfn_conv1x1_persistent_f32(const vfn_conv_desc* d, int cfg, int wgs, void* stream) {
-    if (!d || !d->in || !d->w || !d->out || cfg < 0 || cfg > 7) return VFN_ERR_ARG;
+    if (!d || !d->in || !d->w || !d->out || cfg < 0 || cfg >= kWinoCfgs) return VFN_ERR_ARG;
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->mask || d->in_lp || d->out_lp || d->w_packed || d->ksplit > 1 ||
         d->w_batch_rows || d->Cin % 32 || d->in_ld % 4 || d->M < 1 || d->M != d->N * d->H * d->W) return VFN_ERR_ARG;
-    static const int bn[4] = {128, 128, 64, 64};
-    if (d->cout_pad < (d->Cout + bn[cfg & 3] - 1) / bn[cfg & 3] * bn[cfg & 3]) return VFN_ERR_ARG;
+    const int bn = kWinoTile[cfg & 3][1];
+    if (d->cout_pad < (d->Cout + bn - 1) / bn * bn) return VFN_ERR_ARG;
     const long long lim = 0x7fffff00LL;
     if ((long long)d->M * d->in_ld * 4 >= lim || (long long)d->M * d->out_ld * 4 >= lim || (long long)d->cout_pad * d->Cin * 4 >= lim ||
         (d->res && (long long)(d->res_mod > 0 ? d->res_mod : d->M) * d->res_ld * 4 >= lim)) return VFN_ERR_ARG;
     wino_gemm_args a{d->in, d->w, d->out, 1, d->M, d->Cin, d->Cout, d->cout_pad, 0, 0,
                      d->in_ld, d->out_ld, d->res ? d->res_ld : 0, d->res_mod, d->relu_in, d->relu_out, d->scale, d->shift, d->res};
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_wino_gemm<128, 128, 4, 2, 1, true>(a, wgs, s);
-        case 1: return launch_wino_gemm<64, 128, 2, 4, 1, true>(a, wgs, s);
-        case 2: return launch_wino_gemm<128, 64, 4, 2, 1, true>(a, wgs, s);
-        case 3: return launch_wino_gemm<64, 64, 2, 2, 1, true>(a, wgs, s);
-        case 4: return launch_wino_gemm<128, 128, 4, 2, 2, true>(a, wgs, s);
-        case 5: return launch_wino_gemm<64, 128, 2, 4, 2, true>(a, wgs, s);
-        case 6: return launch_wino_gemm<128, 64, 4, 2, 2, true>(a, wgs, s);
-        case 7: return launch_wino_gemm<64, 64, 2, 2, 2, true>(a, wgs, s);
-    }
-    return VFN_ERR_ARG;
+    return launch_wino_cfg<true, false>(a, cfg, wgs, (hipStream_t)stream);
 }
 
 // (ABI 12) the plain-bf16 mode's Winograd layers (BASELINE configs C3 / C5): the input transform writes V as bf16 (computed in f32, rounded to
@@ -694,23 +683,11 @@ extern "C" int vfn_winograd_input_bf16(const float* x, int N, int H, int W, int 
 
 extern "C" int vfn_winograd_gemm_bf16(const void* V, const void* U, float* Mb, int comps, int rows_pad, int C, int Cout, int cout_pad, int cfg,
                                       int wgs, void* stream) {
-    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 64 || C % 64 || Cout < 1 || cout_pad < Cout || cfg < 0 || cfg > 7) return VFN_ERR_ARG;
-    static const int bm[4] = {128, 64, 128, 64}, bn[4] = {128, 128, 64, 64};
-    const int tc = cfg & 3;
-    if (rows_pad % bm[tc] || cout_pad < (Cout + bn[tc] - 1) / bn[tc] * bn[tc]) return VFN_ERR_ARG;
+    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 64 || C % 64 || Cout < 1 || cout_pad < Cout || cfg < 0 || cfg >= kWinoCfgs) return VFN_ERR_ARG;
+    const int bm = kWinoTile[cfg & 3][0], bn = kWinoTile[cfg & 3][1];
+    if (rows_pad % bm || cout_pad < (Cout + bn - 1) / bn * bn) return VFN_ERR_ARG;
     if ((long long)comps * rows_pad * C * 2 >= 0x7fffff00LL || (long long)comps * cout_pad * C * 2 >= 0x7fffff00LL) return VFN_ERR_ARG;
     wino_gemm_args a{reinterpret_cast<const float*>(V), reinterpret_cast<const float*>(U), Mb, comps, rows_pad, C, Cout, cout_pad, 0, 0, 0, 0, 0, 0, 0, 0,
                      nullptr, nullptr, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    switch (cfg) {
-        case 0: return launch_wino_gemm<128, 128, 4, 2, 1, false, true>(a, wgs, s);
-        case 1: return launch_wino_gemm<64, 128, 2, 4, 1, false, true>(a, wgs, s);
-        case 2: return launch_wino_gemm<128, 64, 4, 2, 1, false, true>(a, wgs, s);
-        case 3: return launch_wino_gemm<64, 64, 2, 2, 1, false, true>(a, wgs, s);
-        case 4: return launch_wino_gemm<128, 128, 4, 2, 2, false, true>(a, wgs, s);
-        case 5: return launch_wino_gemm<64, 128, 2, 4, 2, false, true>(a, wgs, s);
-        case 6: return launch_wino_gemm<128, 64, 4, 2, 2, false, true>(a, wgs, s);
-        case 7: return launch_wino_gemm<64, 64, 2, 2, 2, false, true>(a, wgs, s);
-    }
-    return VFN_ERR_ARG;
+    return launch_wino_cfg<false, true>(a, cfg, wgs, (hipStream_t)stream);
 }

@@ -248,7 +248,7 @@ def tune_desc(d, bf, ws, cnt, iters=3, cfg_filter=None, allow_split=True):
             if best_t is None or t < best_t:
                 best, best_t = (c, 1, 0), t
     for c, (bm, bn) in enumerate(tiles):
-        if bf and c not in ops.BF16_CFGS:              # no LDS-DMA variants (the DMA cannot convert)
+        if c not in ops.conv_cfgs(bf):                 # (the reduced-precision modes have no LDS-DMA variants: the DMA cannot convert)
             continue
         if cfg_filter is not None and not cfg_filter(key, c):
             continue

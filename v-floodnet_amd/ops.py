@@ -39,6 +39,22 @@ def conv_cfg_tpb(cfg):
     return _lib.lib().vfn_conv_cfg_tpb(int(cfg))
 
 
+def conv_cfgs(mode, _cache={}):
+    """Ids of the tile configurations that arithmetic mode ``mode`` (0 f32, 1 bf16, 2 bf16x3) accepts (vfn_conv_cfg_modes)."""
+    mode = int(mode)
+    if mode not in _cache:
+        L = _lib.lib()
+        _cache[mode] = tuple(c for c in range(L.vfn_conv_cfg_count()) if L.vfn_conv_cfg_modes(c) >> mode & 1)
+    return _cache[mode]
+
+
+def __getattr__(name):
+    """``ops.BF16_CFGS``, the name the ids of the reduced-precision modes had as a literal: asked of the library on first use."""
+    if name == 'BF16_CFGS':
+        return conv_cfgs(1)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
 def conv_cfg_kind(cfg):
     """0 = LDS-tiled, 1 = wave-autonomous (conv_direct_kernel), 2 = stream-K (conv_streamk_kernel) -- vfn_conv_cfg_kind."""
     return _lib.lib().vfn_conv_cfg_kind(int(cfg))
@@ -282,9 +298,6 @@ def conv_cfg_name(cfg, mode=0, _cache={}):
     if mode not in _cache:
         _cache[mode] = conv_cfg_names(mode)
     return _cache[mode][cfg]
-
-
-BF16_CFGS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 17, 19, 22, 23) + tuple(range(26, 38))     # (no LDS-DMA variants: the DMA cannot convert)
 
 
 def conv2d_nhwc(x, wp, cout, kh, kw, stride, pad, scale=None, shift=None, res=None,
