@@ -27,9 +27,10 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 15
+#define VFN_ABI_VERSION 16
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
-       VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9 };
+       VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9,
+       VFN_DESC_TRAIN_AUG = 10 };
 int vfn_abi_version(void);
 int vfn_sizeof_desc(int which);
 
@@ -747,6 +748,90 @@ int vfn_waterline_scan(const unsigned char* label, int H, int W, const int* keyp
                        int T, int t, void* stream);
 int vfn_waterlevel_draw_u8(unsigned char* overlay, int H, int W, const int* boxes, int R, const int* log, int T, int t,
                            void* stream);
+
+/* ------------------------------------------------------------------ training clips
+ * Water_Image_Train_DS.__getitem__ (video_module/dataset/Water_DS.py:53-83) builds T frames from one photograph with PIL:
+ * RandomHorizontalFlip, ColorJitter, RandomAffine (video_module/dataset/transforms.py:31-175), RandomResizedCrop (:289-372),
+ * ToTensor and ToOnehot (:383-421).  These entry points do the pixel work for all T frames on the device, one launch per
+ * stage with blockIdx.z = frame, from the decoded uint8 photograph src [H][W][3] and its palette-index mask [H][W].  The
+ * arithmetic is Pillow's (12.2.0), restated operation by operation; no fused multiply-adds; the output equals Pillow's in
+ * every byte.  The host draws the random parameters and builds the small tables (vfloodnet_amd/train_dataset.py).
+ *
+ * vfn_train_aug_frame: the record of one frame.  flip / jitter / affine switch the three transforms on (frame 0 of the
+ *     reference has none).  win = (i, j, h, w): the crop RandomResizedCrop drew, rows i .. i+h-1, columns j .. j+w-1.
+ * vfn_train_aug_jitter   for every frame with jitter != 0: jit[t] [H][W][3] = the four ColorJitter operations in order[0..3]
+ *     (0 brightness, 1 contrast, 2 saturation, 3 hue), each result rounded to uint8, of the (flipped, when flip != 0) source.
+ *     L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (libImaging/Convert.c).  Brightness / contrast / saturation are
+ *     ImageEnhance's Image.blend(degenerate, image, factor) with degenerate = black / the constant int(sum L / N + 0.5)
+ *     (the division in double; L of the image as it stands before that operation) / L replicated; libImaging/Blend.c:
+ *     t = f32(deg) + factor * f32(img - deg) in float; for 0 <= factor <= 1 the result is (uint8)(int)t, else t <= 0 -> 0,
+ *     t >= 255 -> 255, else truncated; factor == 1 copies.  Hue: RGB -> HSV (Convert.c rgb2hsv_row), H = (H + hue_shift) &
+ *     255, HSV -> RGB (hsv2rgb_row), always both ways; hue_shift = int(hue_factor * 255) mod 256.  The sum of L is reduced
+ *     with integer atomics into lsum [T] (one pass; a second pass recomputes and writes).  Two launches and one memset.
+ * vfn_train_aug_affine   win_img[t] [h][w][3] and win_mask[t] [h][w] (tight rows, frame t at offset t*H*W*3 / t*H*W) = the
+ *     window [i:i+h, j:j+w] of Image.transform(size, AFFINE, m, BICUBIC / NEAREST, fillcolor=0) of the jittered (jit[t], when
+ *     jitter != 0) or plain, flipped or not, image and mask: only the pixels the crop will read are evaluated, each exactly as
+ *     the full transform computes it.  affine == 0 copies the window.  Bicubic (libImaging/Geometry.c affine_transform,
+ *     bicubic_filter8), in double: xin = m0 (x + 0.5) + m1 (y + 0.5) + m2, yin likewise; 0 where xin < 0, xin >= W, yin < 0
+ *     or yin >= H; then both minus 0.5, x0 = floor, d = fraction, taps x0-1 .. x0+2 with columns clamped; row y0-1 clamped,
+ *     a row y0 .. y0+2 outside the image repeats the previous row's interpolated value; p1 = v2, p2 = -v1 + v3,
+ *     p3 = 2 (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4, v = p1 + d (p2 + d (p3 + d p4)); <= 0 -> 0, >= 255 -> 255, else
+ *     truncated.  Nearest (affine_fixed): FIX(v) = floor(v 65536 + 0.5), xx = FIX(m2 + m0 0.5 + m1 0.5) + FIX(m1) y + FIX(m0) x
+ *     in 64-bit integers, yy likewise, source (xx >> 16, yy >> 16) or 0 outside; valid while every corner coordinate stays
+ *     below 32768 (else VFN_ERR_ARG).  With nearest_tables != 0 (the caller sets it when m1 == m3 == 0, where Pillow takes
+ *     ImagingScaleAffine instead) the source column / row come from aff_xtab [T][W] / aff_ytab [T][H] (-1: outside).
+ * vfn_train_aug_resize   crop().resize((S, S)) of the window, ToTensor and ToOnehot.  Image (libImaging/Resample.c, 8 bits
+ *     per channel): a horizontal then a vertical pass of out = clip8((2^21 + sum k p) >> 22) with the host's tables: bounds
+ *     [T][S][2] = (first source index, count), coefficients int32 [T][S][ksize] = int(+-0.5 + w 2^22) of the normalised
+ *     a = -0.5 bicubic weights; the horizontal result is rounded to uint8 (hpass [T][H][S][3] scratch).  frames [T][3][S][S]
+ *     = float(u8) / 255.0f.  Mask (Geometry.c ImagingScaleAffine): label = window[ny[oy]][nx[ox]] from index tables int32
+ *     [T][S] the host accumulates (-1: outside, label 0); masks [T][obj_n][S][S]: channel k = (label == obj_list[k-1]) for
+ *     k = 1 .. obj_n-1, channel 0 = 1 - their sum (transforms.py:417-419).  1 <= obj_n <= VFN_TRAIN_AUG_MAX_OBJ.  3 launches.
+ * vfn_train_aug_label_present   present [256] (device) = 1 for every label of mask[ytab[oy]][xtab[ox]], oy, ox < S (index
+ *     tables int32 [S] on the device, absolute source indices, -1: label 0), else 0: the labels ToOnehot's object list is
+ *     built from (transforms.py:405-411), read back by the host (256 bytes) which shuffles them (:413-415).
+ * Every entry returns VFN_ERR_ARG, and launches nothing, for a null pointer it needs, H or W above VFN_TRAIN_AUG_MAX_SIDE, T
+ * above VFN_TRAIN_AUG_MAX_T, S above VFN_TRAIN_AUG_MAX_OUT, a window outside the image, an order that is no permutation, or
+ * obj_n outside its range. */
+#define VFN_TRAIN_AUG_MAX_T 16
+#define VFN_TRAIN_AUG_MAX_SIDE 8192
+#define VFN_TRAIN_AUG_MAX_OUT 4096
+#define VFN_TRAIN_AUG_MAX_OBJ 11
+typedef struct {
+    double m[6];                             /* inverse affine matrix (output -> source pixel), torchvision's */
+    float brightness, contrast, saturation;  /* blend factors */
+    int hue_shift;                           /* 0 .. 255 */
+    int order[4];
+    int flip, jitter, affine, nearest_tables;
+    int win_i, win_j, win_h, win_w;
+} vfn_train_aug_frame;
+typedef struct {
+    const unsigned char* src;                /* [H][W][3] */
+    const unsigned char* mask;               /* [H][W] */
+    unsigned char* jit;                      /* [T][H][W][3] */
+    unsigned long long* lsum;                /* [T] */
+    unsigned char* win_img;                  /* [T][H*W*3] */
+    unsigned char* win_mask;                 /* [T][H*W] */
+    const int* aff_xtab;                     /* [T][W], or null when no frame sets nearest_tables */
+    const int* aff_ytab;                     /* [T][H] */
+    unsigned char* hpass;                    /* [T][H][S][3] */
+    const int* kx_bounds;                    /* [T][S][2] */
+    const int* kx;                           /* [T][S][ksize_x] */
+    const int* ky_bounds;
+    const int* ky;                           /* [T][S][ksize_y] */
+    const int* nx;                           /* [T][S] */
+    const int* ny;
+    float* frames;                           /* [T][3][S][S] */
+    float* masks;                            /* [T][obj_n][S][S] */
+    int H, W, T, S, ksize_x, ksize_y, obj_n;
+    int obj_list[VFN_TRAIN_AUG_MAX_OBJ - 1]; /* labels 1 .. 255 of channels 1 .. obj_n-1 */
+    vfn_train_aug_frame frame[VFN_TRAIN_AUG_MAX_T];
+} vfn_train_aug_desc;
+int vfn_train_aug_jitter(const vfn_train_aug_desc* d, void* stream);
+int vfn_train_aug_affine(const vfn_train_aug_desc* d, void* stream);
+int vfn_train_aug_resize(const vfn_train_aug_desc* d, void* stream);
+int vfn_train_aug_label_present(const unsigned char* mask, int H, int W, const int* xtab, const int* ytab, int S,
+                                unsigned char* present, void* stream);
 
 #ifdef __cplusplus
 }

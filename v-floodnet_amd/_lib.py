@@ -100,8 +100,27 @@ class BankDesc(C.Structure):
                 ('obj_n', C.c_int), ('cap', C.c_int), ('rm_class', C.c_int), ('rm_request', C.c_int)]
 
 
-ABI_VERSION = 15         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
-DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc}     # vfn_sizeof_desc(which)
+class TrainAugFrame(C.Structure):
+    _fields_ = [('m', C.c_double * 6), ('brightness', C.c_float), ('contrast', C.c_float), ('saturation', C.c_float),
+                ('hue_shift', C.c_int), ('order', C.c_int * 4),
+                ('flip', C.c_int), ('jitter', C.c_int), ('affine', C.c_int), ('nearest_tables', C.c_int),
+                ('win_i', C.c_int), ('win_j', C.c_int), ('win_h', C.c_int), ('win_w', C.c_int)]
+
+
+TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = 16, 8192, 4096, 11     # include/vfn_hip.h
+
+
+class TrainAugDesc(C.Structure):
+    _fields_ = [('src', c_fp), ('mask', c_fp), ('jit', c_fp), ('lsum', c_fp), ('win_img', c_fp), ('win_mask', c_fp),
+                ('aff_xtab', c_fp), ('aff_ytab', c_fp), ('hpass', c_fp), ('kx_bounds', c_fp), ('kx', c_fp),
+                ('ky_bounds', c_fp), ('ky', c_fp), ('nx', c_fp), ('ny', c_fp), ('frames', c_fp), ('masks', c_fp),
+                ('H', C.c_int), ('W', C.c_int), ('T', C.c_int), ('S', C.c_int), ('ksize_x', C.c_int), ('ksize_y', C.c_int),
+                ('obj_n', C.c_int), ('obj_list', C.c_int * (TRAIN_AUG_MAX_OBJ - 1)),
+                ('frame', TrainAugFrame * TRAIN_AUG_MAX_T)]
+
+
+ABI_VERSION = 16         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
+DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc, 10: TrainAugDesc}     # vfn_sizeof_desc(which)
 
 
 def lib():
@@ -159,6 +178,8 @@ def _declare(L):
     L.vfn_bank_refresh_lp.argtypes = [C.POINTER(BankDesc), p, p, i, p]
     L.vfn_bank_refresh_lp_keys.argtypes = [C.POINTER(BankDesc), p, i, p]
     L.vfn_bank_match_certified.argtypes = [C.POINTER(BankMatchDesc), p]
+    for name in ('vfn_train_aug_jitter', 'vfn_train_aug_affine', 'vfn_train_aug_resize'):
+        getattr(L, name).argtypes = [C.POINTER(TrainAugDesc), p]
     L.vfn_stem_wgrad_scratch_floats.argtypes = [i]
     L.vfn_stem_wgrad_scratch_floats.restype = i
     for name, args in SIGNATURES.items():
@@ -242,6 +263,7 @@ SIGNATURES = {
     'vfn_warp_perspective_f32': [_p, _p, _i, _i, C.POINTER(C.c_double), _p],
     'vfn_waterline_scan': [_p, _i, _i, C.POINTER(_i), _i, _i, _p, _i, _i, _p],
     'vfn_waterlevel_draw_u8': [_p, _i, _i, C.POINTER(_i), _i, _p, _i, _i, _p],
+    'vfn_train_aug_label_present': [_p, _i, _i, _p, _p, _i, _p, _p],
 }
 # every symbol include/vfn_hip.h declares (checked by tests/test_abi.py)
 ALL_SYMBOLS = sorted(list(SIGNATURES) + [
@@ -249,7 +271,7 @@ ALL_SYMBOLS = sorted(list(SIGNATURES) + [
     'vfn_stem_conv7x7_f32',
     'vfn_bank_scan', 'vfn_memread_apply', 'vfn_memread_finish', 'vfn_bank_merge', 'vfn_bank_append', 'vfn_bank_remove', 'vfn_bank_refresh_norms', 'vfn_bank_refresh_lp', 'vfn_conv_wgrad_f32',
     'vfn_bank_refresh_lp_keys', 'vfn_bank_match_certified',
-    'vfn_stem_wgrad_scratch_floats'])
+    'vfn_stem_wgrad_scratch_floats', 'vfn_train_aug_jitter', 'vfn_train_aug_affine', 'vfn_train_aug_resize'])
 
 
 def check(status, what):

@@ -5,6 +5,7 @@
 // 4: PNG / JPEG / segment-uncertainty / norm-refresh entry points (round 2)
 // 13: vfn_bankmatch_desc, vfn_bank_match_certified, vfn_bank_refresh_lp_keys
 // 15: vfn_conv_cfg_modes
+// 16: vfn_train_aug_desc, vfn_train_aug_* (training clips)
 extern "C" int vfn_abi_version(void) { return VFN_ABI_VERSION; }
 
 // sizeof of every descriptor as THIS library was compiled: a binding whose struct layout drifted fails its
@@ -21,6 +22,7 @@ extern "C" int vfn_sizeof_desc(int which) {
         case VFN_DESC_REFRESH_EPILOGUE: return (int)sizeof(vfn_refresh_epilogue);
         case VFN_DESC_GATHER: return (int)sizeof(vfn_gather_entry);
         case VFN_DESC_BANKMATCH: return (int)sizeof(vfn_bankmatch_desc);
+        case VFN_DESC_TRAIN_AUG: return (int)sizeof(vfn_train_aug_desc);
     }
     return -1;
 }

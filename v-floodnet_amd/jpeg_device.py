@@ -41,9 +41,9 @@ def entropy_decode(data):
 _plane_cache = {}
 
 
-def to_tensor(coef, qt, info, device, out=None, want_u8=False):
+def to_tensor(coef, qt, info, device, out=None, want_u8=False, u8_only=False):
     """Coefficients (host or device tensors / arrays from ``entropy_decode``) -> float32 [3,H,W] in [0,1] on ``device``
-    (and, with ``want_u8``, the RGB uint8 [H,W,3] image as well)."""
+    (and, with ``want_u8``, the RGB uint8 [H,W,3] image as well; with ``u8_only``, that image alone)."""
     L = _lib.lib()
     info = np.asarray(info).astype(np.int64).reshape(-1)
     W, H, ncomp, hmax, vmax = (int(info[i]) for i in range(5))
@@ -61,14 +61,16 @@ def to_tensor(coef, qt, info, device, out=None, want_u8=False):
                                  bpr, brows, bpr * 8, stream()), 'vfn_jpeg_idct_u8')
         planes.append(pl)
         off += bpr * brows * 64
-    if out is None:
+    if out is None and not u8_only:
         out = torch.empty(3, H, W, dtype=torch.float32, device=device)
-    u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=device) if want_u8 else None
+    u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=device) if want_u8 or u8_only else None
     hs = hmax // int(info[11]) if ncomp == 3 else 1
     vs = vmax // int(info[12]) if ncomp == 3 else 1
     check(L.vfn_jpeg_to_tensor_f32(ptr(planes[0]), ptr(planes[1]) if ncomp == 3 else None, ptr(planes[2]) if ncomp == 3 else None,
                                    planes[0].shape[1], planes[1].shape[1] if ncomp == 3 else 0, W, H, hs, vs, ncomp,
                                    ptr(out), ptr(u8), stream()), 'vfn_jpeg_to_tensor_f32')
+    if u8_only:
+        return u8
     return (out, u8) if want_u8 else out
 
 

@@ -59,9 +59,8 @@ def inflate(data):
 _work_cache = {}
 
 
-def to_tensor(filtered, info, palette, device, want_u8=False):
-    """Inflated scanlines (host or device tensors / arrays from ``inflate``) -> float32 [3,H,W] in [0,1] on ``device``
-    (and, with ``want_u8``, the RGB uint8 [H,W,3] image as well)."""
+def _unfilter(filtered, info, device):
+    """Inflated scanlines -> (raw uint8 [H, pitch] in this stream's cached buffer, pitch, W, H, colour type)."""
     L = _lib.lib()
     W, H, ctype, bpp = (int(v) for v in np.asarray(info).reshape(-1)[:4])
     pitch, wb = _lib.C.c_int(), _lib.C.c_longlong()
@@ -74,12 +73,27 @@ def to_tensor(filtered, info, palette, device, want_u8=False):
                             torch.zeros(1, dtype=torch.int32, device=device))
     work, raw, status = _work_cache[key]
     check(L.vfn_png_unfilter_u8(ptr(f_d), W, H, bpp, ptr(work), ptr(raw), ptr(status), stream()), 'vfn_png_unfilter_u8')
+    return raw, pitch.value, W, H, ctype
+
+
+def to_tensor(filtered, info, palette, device, want_u8=False):
+    """Inflated scanlines (host or device tensors / arrays from ``inflate``) -> float32 [3,H,W] in [0,1] on ``device``
+    (and, with ``want_u8``, the RGB uint8 [H,W,3] image as well)."""
+    raw, pitch, W, H, ctype = _unfilter(filtered, info, device)
     pal_d = torch.as_tensor(palette).to(device=device, dtype=torch.uint8, non_blocking=True).reshape(-1) if ctype == 3 else None
     out = torch.empty(3, H, W, dtype=torch.float32, device=device)
     u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=device) if want_u8 else None
-    check(L.vfn_png_to_tensor_f32(ptr(raw), pitch.value, W, H, ctype, ptr(pal_d), ptr(out), ptr(u8), stream()),
+    check(_lib.lib().vfn_png_to_tensor_f32(ptr(raw), pitch, W, H, ctype, ptr(pal_d), ptr(out), ptr(u8), stream()),
           'vfn_png_to_tensor_f32')
     return (out, u8) if want_u8 else out
+
+
+def palette_indices(filtered, info, device):
+    """Inflated scanlines of a palette (colour type 3) file -> its indices, uint8 [H,W] on ``device``: PIL's mode 'P' pixels."""
+    raw, pitch, W, H, ctype = _unfilter(filtered, info, device)
+    if ctype != 3:
+        raise RuntimeError('not a palette PNG')
+    return raw.view(H, pitch)[:, :W].clone()
 
 
 def check_status(device):
