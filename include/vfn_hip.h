@@ -27,7 +27,7 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 16
+#define VFN_ABI_VERSION 17
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
        VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9,
        VFN_DESC_TRAIN_AUG = 10 };
@@ -748,6 +748,54 @@ int vfn_waterline_scan(const unsigned char* label, int H, int W, const int* keyp
                        int T, int t, void* stream);
 int vfn_waterlevel_draw_u8(unsigned char* overlay, int H, int W, const int* boxes, int R, const int* log, int T, int t,
                            void* stream);
+
+/* ------------------------------------------------------------------ the reference boxes followed through the clip
+ * estimation/reference_tracking.py:104-107, :183-188 run cv2.TrackerCSRT over every (warped) frame and scan the waterline under
+ * the box it returns.  This tracker is NOT CSRT and claims no agreement with OpenCV's boxes: it is translation-only, zero-mean
+ * normalised cross-correlation against a slowly adapting template, with no scale or rotation adaptation, stated in integers:
+ *   luma    from the loop's frame float [3][H][W]: each sample a byte as vfn_overlay_u8 makes it (truncation of the f32 product
+ *           x * 255.0f), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, uint8 [H][W].
+ *   state   per reference r: box (x, y, w, h) int32, w and h fixed for the clip, 1 <= w, h <= VFN_TRACK_MAX_SIDE; template T16
+ *           uint16 [h][w] in 8.8 fixed point.
+ *   init    the box must lie inside the image; T16 = L[y:y+h, x:x+w] << 8.
+ *   update  (every frame, the one of init included) candidates (dx, dy), |dx|, |dy| <= S, 1 <= S <= VFN_TRACK_MAX_RADIUS,
+ *           visited dy ascending, then dx ascending; one whose window [x+dx, x+dx+w) x [y+dy, y+dy+h) leaves the image is
+ *           skipped.  With P the window's luma and N = w h, exact in int64: A = sum T16, B = sum P, C = sum T16 P,
+ *           D = sum T16^2, E = sum P^2, num = N C - A B, vp = N E - B^2; a candidate with vp == 0 is skipped.
+ *           key = double(num) * fabs(double(num)) / double(vp), float64, no fused multiply-adds, correctly rounded division.
+ *           The largest key wins, on ties the first visited.  With vt = double(N) double(D) - double(A) double(A) the update
+ *           FAILS when there is no candidate, vt <= 0, num <= 0, or double(num)^2 < 0.25 (vt double(vp)) (a correlation below
+ *           0.5): box and template stay, the flag is 0.  Otherwise the flag is 1, the box moves by (dx, dy) and, with P the
+ *           window at the new position, T16 += ((P << 8) - T16 + 8) >> 4 (arithmetic shift of the signed difference).
+ *   logs    row t of box_log int32 [T][R][4], ok_log int32 [T][R] and score_log float [T][R] = float(num / sqrt(vt vp)), or 0
+ *           without a candidate (for people to read; the only value that is not pinned to the bit).
+ * A box that leaves the search radius within one frame is lost until it comes back inside it.
+ *
+ * vfn_track_luma_f32  frame -> luma.
+ * vfn_track_init      boxes int32 [R][4] on the HOST, R <= VFN_WL_MAX_REFS.  Device buffers of the state: box_state int32 [R][4];
+ *     t16 uint16, reference r's template at element sum_{q<r} w_q h_q, t16_elems >= sum w h; acc uint64 [R][(2S+1)^2][3], the
+ *     search's sums, acc_elems >= that (zeroed here, left zero by every update).
+ * vfn_track_update    one call per frame for all R references: two launches (search: 256 candidates x one 64 x 32 template
+ *     tile per workgroup; finish: one workgroup per reference).  sizes int32 [R][2] = (w, h) on the HOST, those of init; x, y
+ *     are read from box_state on the device, and nothing is reported to the host.
+ * vfn_waterline_scan_dev, vfn_waterlevel_draw_dev   vfn_waterline_scan and vfn_waterlevel_draw_u8 with boxes int32 [R][4] read
+ *     from DEVICE memory (a row of box_log).  Key point: kx = (int)(x + w / 2.0), ky = y + h, computed on the device; one with
+ *     kx outside [0, W), ky < 0 or ky >= H - 1 logs -1 and reads nothing.  A box with w or h < 0 or a value beyond +-2^24 is
+ *     not drawn.
+ * Every entry returns VFN_ERR_ARG, and launches nothing, for a null pointer, a size outside the caps or the buffers, a box
+ * outside the image at init, or t outside [0, T). */
+#define VFN_TRACK_MAX_SIDE 512
+#define VFN_TRACK_MAX_RADIUS 32
+int vfn_track_luma_f32(const float* frame, unsigned char* luma, int H, int W, void* stream);
+int vfn_track_init(const unsigned char* luma, int H, int W, const int* boxes, int R, int S, int* box_state, unsigned short* t16,
+                   long long t16_elems, unsigned long long* acc, long long acc_elems, void* stream);
+int vfn_track_update(const unsigned char* luma, int H, int W, const int* sizes, int R, int S, int* box_state, unsigned short* t16,
+                     long long t16_elems, unsigned long long* acc, long long acc_elems, int* box_log, int* ok_log,
+                     float* score_log, int T, int t, void* stream);
+int vfn_waterline_scan_dev(const unsigned char* label, int H, int W, const int* boxes, int R, int water_label, int* log, int T,
+                           int t, void* stream);
+int vfn_waterlevel_draw_dev(unsigned char* overlay, int H, int W, const int* boxes, int R, const int* log, int T, int t,
+                            void* stream);
 
 /* ------------------------------------------------------------------ training clips
  * Water_Image_Train_DS.__getitem__ (video_module/dataset/Water_DS.py:53-83) builds T frames from one photograph with PIL:

@@ -1,7 +1,8 @@
 """End-to-end rate of the drop-in loop ``vfloodnet_amd.video_seg.main`` (PNG frames on disk -> mask / overlay PNGs on
 disk), the part of the path the kernel benchmark leaves out.  usage: main_throughput.py [frames] [viz 0|1]; FRAME_FMT=png
 writes the input frames as PNG instead of JPEG; DECODE=pil decodes them with PIL in the workers; WATERLEVEL=1 adds
-``--waterlevel`` with two static reference boxes and a mild keystone homography (waterlevel.csv and viz/ in the same pass)"""
+``--waterlevel`` with two reference boxes and a mild keystone homography (waterlevel.csv and viz/ in the same pass); TRACK=1
+adds ``--track on`` to it (the boxes follow the frame)"""
 import sys, os, time, argparse, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, vfloodnet_amd
@@ -32,6 +33,8 @@ if os.environ.get('WATERLEVEL') == '1':
     np.savetxt('ref_bbox.txt', np.array([(200, 60, 40, 90), (560, 80, 50, 70)]), '%.4f')
     np.savetxt('homo_mat.txt', np.array([[1.02, 0.05, -3.0], [0.01, 0.98, 2.0], [1e-4, 2e-4, 1.0]]), '%.4f')
     args = argparse.Namespace(**vars(args), waterlevel=True, ref_bbox='ref_bbox.txt', homo_mat='homo_mat.txt')
+    if os.environ.get('TRACK') == '1':
+        args = argparse.Namespace(**vars(args), track='on', track_radius=16)
 dev = torch.device('cuda', 0)
 video_seg.main(argparse.Namespace(**{**vars(args), 'test_name': 'warm'}) if False else args, dev)   # warm-up (plans, tables, page cache)
 # time the frame loop from iteration SKIP+1 to the end (files flushed), so that model construction, checkpoint loading
@@ -49,4 +52,4 @@ video_seg.main(args, dev)
 dt = time.perf_counter() - marks['t0']
 T = T - SKIP
 print('main() frame loop: %d frames, viz=%s%s: %.1f frames/s end to end, files on disk (%.1f ms/frame)'
-      % (T - 1, viz, ', waterlevel' if getattr(args, 'waterlevel', False) else '', (T - 1) / dt, 1e3 * dt / (T - 1)))
+      % (T - 1, viz, (', waterlevel' if getattr(args, 'waterlevel', False) else '') + (', track' if getattr(args, 'track', 'off') == 'on' else ''), (T - 1) / dt, 1e3 * dt / (T - 1)))

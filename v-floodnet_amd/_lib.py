@@ -119,7 +119,7 @@ class TrainAugDesc(C.Structure):
                 ('frame', TrainAugFrame * TRAIN_AUG_MAX_T)]
 
 
-ABI_VERSION = 16         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
+ABI_VERSION = 17         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
 DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc, 10: TrainAugDesc}     # vfn_sizeof_desc(which)
 
 
@@ -263,6 +263,11 @@ SIGNATURES = {
     'vfn_warp_perspective_f32': [_p, _p, _i, _i, C.POINTER(C.c_double), _p],
     'vfn_waterline_scan': [_p, _i, _i, C.POINTER(_i), _i, _i, _p, _i, _i, _p],
     'vfn_waterlevel_draw_u8': [_p, _i, _i, C.POINTER(_i), _i, _p, _i, _i, _p],
+    'vfn_track_luma_f32': [_p, _p, _i, _i, _p],
+    'vfn_track_init': [_p, _i, _i, C.POINTER(_i), _i, _i, _p, _p, _ll, _p, _ll, _p],
+    'vfn_track_update': [_p, _i, _i, C.POINTER(_i), _i, _i, _p, _p, _ll, _p, _ll, _p, _p, _p, _i, _i, _p],
+    'vfn_waterline_scan_dev': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p],
+    'vfn_waterlevel_draw_dev': [_p, _i, _i, _p, _i, _p, _i, _i, _p],
     'vfn_train_aug_label_present': [_p, _i, _i, _p, _p, _i, _p, _p],
 }
 # every symbol include/vfn_hip.h declares (checked by tests/test_abi.py)

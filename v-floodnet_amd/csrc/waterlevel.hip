@@ -3,7 +3,8 @@
 //   vfn_warp_perspective_f32  0) as OpenCV's fixed-point remap, stated in integers (:169-170)
 //   vfn_waterline_scan        the column scan below each reference's key point (:195-204)
 //   vfn_waterlevel_draw_u8    the green boxes and red lines of the annotated overlay (:193, :203), by the project's own rule
-// All three are bandwidth-trivial (about 3 MB per 480p frame); they exist so that the water-level series comes out of the
+//   vfn_waterline_scan_dev, vfn_waterlevel_draw_dev    the same two under boxes read from device memory (csrc/track.hip)
+// All of them are bandwidth-trivial (about 3 MB per 480p frame); they exist so that the water-level series comes out of the
 // pass that writes the masks, on the PNG sink's side stream, without a host synchronisation per frame.
 #include "common.h"
 #include "../../include/vfn_hip.h"
@@ -73,10 +74,9 @@ __global__ void warp_f32_kernel(const float* __restrict__ src, float* __restrict
 }
 
 // one wavefront per reference: lanes stride over the rows below the key point, a ballot picks the first water row
-__global__ void __launch_bounds__(64) waterline_scan_kernel(const unsigned char* __restrict__ label, int H, int W, WlRefs K,
-                                                            int water_label, int* __restrict__ log_row) {
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const int kx = K.v[r][0], ky = K.v[r][1];
+__device__ __forceinline__ void scan_column(const unsigned char* __restrict__ label, int H, int W, int kx, int ky, int water_label,
+                                            int* __restrict__ out) {
+    const int lane = threadIdx.x;
     int found = -1;
     for (int base = ky + 1; base < H; base += 64) {                 // (base is wave-uniform)
         const int row = base + lane;
@@ -87,26 +87,52 @@ __global__ void __launch_bounds__(64) waterline_scan_kernel(const unsigned char*
             break;
         }
     }
-    if (lane == 0) log_row[r] = found;
+    if (lane == 0) *out = found;
+}
+
+__global__ void __launch_bounds__(64) waterline_scan_kernel(const unsigned char* __restrict__ label, int H, int W, WlRefs K,
+                                                            int water_label, int* __restrict__ log_row) {
+    const int r = blockIdx.x;
+    scan_column(label, H, W, K.v[r][0], K.v[r][1], water_label, log_row + r);
+}
+
+// the same under boxes that live on the device (the row the tracker just wrote): the key point is computed here, and one
+// that does not have a row of the image below it logs -1 and reads nothing
+__global__ void __launch_bounds__(64) waterline_scan_dev_kernel(const unsigned char* __restrict__ label, int H, int W,
+                                                                const int* __restrict__ boxes, int water_label,
+                                                                int* __restrict__ log_row) {
+    const int r = blockIdx.x;
+    const double kx = trunc(boxes[4 * r] + boxes[4 * r + 2] / 2.0);
+    const long long ky = (long long)boxes[4 * r + 1] + boxes[4 * r + 3];
+    if (!(kx >= 0 && kx < W) || ky < 0 || ky >= H - 1) {
+        if (threadIdx.x == 0) log_row[r] = -1;
+        return;
+    }
+    scan_column(label, H, W, (int)kx, (int)ky, water_label, log_row + r);
 }
 
 // in place on the RGB overlay.  Box r: the pixels of the closed rectangle [x, x+w] x [y, y+h] whose distance to its boundary
 // is 0 or 1 pixel, (0, 200, 0).  Line r, when the scan found d > 1: columns kx, kx+1, rows ky .. ky+d, (200, 0, 0); lines
 // after all boxes.  One thread per pixel, so clipping to the image is implicit; only covered pixels are written.
-__global__ void waterlevel_draw_kernel(unsigned char* __restrict__ img, int H, int W, WlRefs B, const int* __restrict__ log_row) {
+// box(r, v) fills v = (x, y, w, h) of reference r and says whether it is drawn
+template <typename Box>
+__device__ __forceinline__ void draw_pixel(unsigned char* __restrict__ img, int H, int W, int R, Box box,
+                                           const int* __restrict__ log_row) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W) return;
     const int py = i / W, px = i - py * W;
     int colour = 0;                                                 // 0 none, 1 box, 2 line
-    for (int r = 0; r < B.n; ++r) {
-        const int x = B.v[r][0], y = B.v[r][1], w = B.v[r][2], h = B.v[r][3];
+    int v[4];
+    for (int r = 0; r < R; ++r) {
+        if (!box(r, v)) continue;
+        const int x = v[0], y = v[1], w = v[2], h = v[3];
         if (px >= x && px <= x + w && py >= y && py <= y + h &&
             min(min(px - x, x + w - px), min(py - y, y + h - py)) < 2) colour = 1;
     }
-    for (int r = 0; r < B.n; ++r) {
+    for (int r = 0; r < R; ++r) {
         const int d = log_row[r];
-        if (d <= 1) continue;
-        const int kx = (int)(B.v[r][0] + B.v[r][2] / 2.0), ky = B.v[r][1] + B.v[r][3];
+        if (d <= 1 || !box(r, v)) continue;
+        const int kx = (int)(v[0] + v[2] / 2.0), ky = v[1] + v[3];
         if ((px == kx || px == kx + 1) && py >= ky && py <= ky + d) colour = 2;
     }
     if (colour) {
@@ -115,6 +141,26 @@ __global__ void waterlevel_draw_kernel(unsigned char* __restrict__ img, int H, i
         p[1] = colour == 1 ? 200 : 0;
         p[2] = 0;
     }
+}
+
+__global__ void waterlevel_draw_kernel(unsigned char* __restrict__ img, int H, int W, WlRefs B, const int* __restrict__ log_row) {
+    draw_pixel(img, H, W, B.n, [&](int r, int* v) {
+        for (int k = 0; k < 4; ++k) v[k] = B.v[r][k];
+        return true;
+    }, log_row);
+}
+
+// boxes int32 [R][4] on the device; a box the host entry point would refuse (w or h < 0, a value beyond +-2^24) is not drawn
+__global__ void waterlevel_draw_dev_kernel(unsigned char* __restrict__ img, int H, int W, const int* __restrict__ boxes, int R,
+                                           const int* __restrict__ log_row) {
+    draw_pixel(img, H, W, R, [&](int r, int* v) {
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) {
+            v[k] = boxes[4 * r + k];
+            ok = ok && v[k] >= (k < 2 ? -(1 << 24) : 0) && v[k] <= (1 << 24);
+        }
+        return ok;
+    }, log_row);
 }
 
 bool warp_args(const void* src, const void* dst, int H, int W, const double* minv, WarpMat& M) {
@@ -176,5 +222,23 @@ extern "C" int vfn_waterlevel_draw_u8(unsigned char* overlay, int H, int W, cons
     }
     hipLaunchKernelGGL(waterlevel_draw_kernel, dim3(cdiv(H * W, 256)), dim3(256), 0, (hipStream_t)stream, overlay, H, W, B,
                        log + (size_t)t * R);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_waterline_scan_dev(const unsigned char* label, int H, int W, const int* boxes, int R, int water_label, int* log,
+                                      int T, int t, void* stream) {
+    if (!label || !boxes || !log || H < 1 || W < 1 || (long long)H * W > INT_MAX / 4 || R < 1 || R > VFN_WL_MAX_REFS ||
+        water_label < 0 || water_label > 255 || t < 0 || t >= T) return VFN_ERR_ARG;
+    hipLaunchKernelGGL(waterline_scan_dev_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, label, H, W, boxes, water_label,
+                       log + (size_t)t * R);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_waterlevel_draw_dev(unsigned char* overlay, int H, int W, const int* boxes, int R, const int* log, int T, int t,
+                                       void* stream) {
+    if (!overlay || !boxes || !log || H < 1 || W < 1 || (long long)H * W > INT_MAX / 4 || R < 1 || R > VFN_WL_MAX_REFS ||
+        t < 0 || t >= T) return VFN_ERR_ARG;
+    hipLaunchKernelGGL(waterlevel_draw_dev_kernel, dim3(cdiv(H * W, 256)), dim3(256), 0, (hipStream_t)stream, overlay, H, W, boxes,
+                       R, log + (size_t)t * R);
     return vfn_check_launch();
 }

@@ -32,6 +32,10 @@ def get_parser(argv=None):
     parser.add_argument('--homo-mat', type=str, default=None, help='3 x 3 homography file (default: records/groundtruth/<name>/homo_mat.txt).')
     parser.add_argument('--no-calib', action='store_true', help='No perspective calibration, whatever the test name.')
     parser.add_argument('--no-viz', dest='viz', action='store_false', default=True, help='Skip the annotated overlays under viz/.')
+    parser.add_argument('--track', choices=['off', 'on', 'auto'], default='off',
+                        help='Follow the reference boxes through the clip (a translation-only correlation tracker, not CSRT). '
+                             'auto: the reference\'s rule by test name (off for houston and LSU).')
+    parser.add_argument('--track-radius', type=int, default=16, help='Search radius of the tracker in pixels per frame (1 .. 32).')
     return parser.parse_args(argv)
 
 
@@ -44,9 +48,16 @@ def use_calibration(args):
     return waterlevel.calibration_default(args.test_name)
 
 
+def use_tracking(args):
+    """``--track``: on, off, or the reference's rule by test name."""
+    mode = getattr(args, 'track', 'off') or 'off'
+    return waterlevel.tracking_default(args.test_name) if mode == 'auto' else mode == 'on'
+
+
 def est_by_reference(img_list, water_mask_list, out_dir, record_dir, test_name, device=None, ref_bbox_path=None,
-                     homo_mat_path=None, calib=None, viz=True):
-    """reference_tracking.py:116-218 without the pickers, the tracker and the plot; returns the ``WaterLevelMeter``."""
+                     homo_mat_path=None, calib=None, viz=True, track=False, track_radius=16):
+    """reference_tracking.py:116-218 without the pickers and the plot, with the project's own tracker in CSRT's place when
+    ``track`` is set (the frames are then loaded without ``viz`` too); returns the ``WaterLevelMeter``."""
     if len(img_list) != len(water_mask_list):
         raise ValueError(f'{len(img_list)} frames but {len(water_mask_list)} masks')
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -55,7 +66,7 @@ def est_by_reference(img_list, water_mask_list, out_dir, record_dir, test_name, 
     viz_dir = os.path.join(out_dir, 'viz')
     if viz:
         os.makedirs(viz_dir, exist_ok=True)
-    meter = waterlevel.WaterLevelMeter(boxes, homo, frames_hint=len(img_list), device=device)
+    meter = waterlevel.WaterLevelMeter(boxes, homo, frames_hint=len(img_list), device=device, track=track, track_radius=track_radius)
     writer = AsyncWriter(4)
     with torch.cuda.device(device):
         sink = PngSink(device, writer)
@@ -63,7 +74,7 @@ def est_by_reference(img_list, water_mask_list, out_dir, record_dir, test_name, 
             name = os.path.basename(img_path)[:-4]
             label = torch.from_numpy(np.array(load_image_in_PIL(mask_path, 'P'), np.uint8)).to(device)
             frame = None
-            if viz:
+            if viz or track:
                 rgb = torch.from_numpy(np.array(load_image_in_PIL(img_path, 'RGB'), np.uint8)).to(device)
                 if tuple(rgb.shape[:2]) != tuple(label.shape):
                     raise ValueError(f'{img_path} is {tuple(rgb.shape[:2])}, its mask {mask_path} {tuple(label.shape)}')
@@ -88,7 +99,7 @@ def main(args, device=None):
         device = torch.device('cuda', getattr(args, 'gpu', 0))
     return est_by_reference(img_list, water_mask_list, out_dir, './records/groundtruth', args.test_name, device,
                             getattr(args, 'ref_bbox', None), getattr(args, 'homo_mat', None), use_calibration(args),
-                            getattr(args, 'viz', True))
+                            getattr(args, 'viz', True), use_tracking(args), getattr(args, 'track_radius', 16))
 
 
 if __name__ == '__main__':

@@ -859,3 +859,118 @@ def waterlevel_draw(overlay, boxes, log, t):
     check(_lib.lib().vfn_waterlevel_draw_u8(ptr(overlay), H, W, bx, R, ptr(log), log.shape[0], int(t), stream()),
           'vfn_waterlevel_draw_u8')
     return overlay
+
+
+# --------------------------------------------------------------------------- reference boxes followed through the clip
+TRACK_MAX_SIDE, TRACK_MAX_RADIUS = 512, 32          # include/vfn_hip.h
+
+
+def track_luma(frame, out=None):
+    """The tracker's luma uint8 [H,W] of the loop's frame float32 [3,H,W] in [0,1] (include/vfn_hip.h states the arithmetic)."""
+    _lib.require_gpu(frame, 'track_luma: frame')
+    if frame.dtype != torch.float32 or frame.dim() != 3 or frame.shape[0] != 3 or not frame.is_contiguous():
+        raise ValueError(f'track_luma: frame must be a contiguous float32 [3,H,W] tensor, got {frame.dtype} {tuple(frame.shape)}')
+    _, H, W = frame.shape
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.uint8, device=frame.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or not out.is_contiguous() or out.device != frame.device:
+        raise ValueError('track_luma: out must be a contiguous uint8 [H,W] tensor beside the frame')
+    check(_lib.lib().vfn_track_luma_f32(ptr(frame), ptr(out), H, W, stream()), 'vfn_track_luma_f32')
+    return out
+
+
+class TrackState:
+    """What the tracker keeps on the device between two frames: ``box`` int32 [R,4], ``t16`` the templates uint16 (8.8 fixed
+    point, reference r's [h,w] at ``offsets[r]``) and ``acc``, the search's sums (zero between two updates)."""
+
+    def __init__(self, boxes, radius, device):
+        import numpy as np
+        self.radius = int(radius)
+        self.R = boxes.shape[0]
+        self.sizes = np.ascontiguousarray(boxes[:, 2:], dtype=np.int32)
+        area = self.sizes[:, 0].astype(np.int64) * self.sizes[:, 1]
+        self.offsets = [int(v) for v in np.concatenate([[0], np.cumsum(area)])]
+        self.box = torch.zeros(self.R, 4, dtype=torch.int32, device=device)
+        self.t16 = torch.zeros(max(1, self.offsets[-1]), dtype=torch.int16, device=device)         # (the bits of a uint16)
+        self.acc = torch.zeros(self.R * (2 * self.radius + 1) ** 2 * 3, dtype=torch.int64, device=device)
+
+    def template(self, r):
+        """Reference r's template as int64 [h,w] on the host (one D2H; for tests and inspection)."""
+        w, h = (int(v) for v in self.sizes[r])
+        return (self.t16[self.offsets[r]:self.offsets[r + 1]].cpu().numpy().view('uint16').astype('int64')).reshape(h, w)
+
+
+def _luma_args(luma, what):
+    _lib.require_gpu(luma, f'{what}: luma')
+    if luma.dtype != torch.uint8 or luma.dim() != 2 or not luma.is_contiguous():
+        raise ValueError(f'{what}: luma must be a contiguous uint8 [H,W] tensor')
+    return luma.shape
+
+
+def track_init(luma, boxes, radius=16):
+    """A ``TrackState`` for the reference boxes (host integers [R][4] = x, y, w, h, inside the image, sides 1 ..
+    ``TRACK_MAX_SIDE``) with the templates cut out of ``luma``; ``radius``: the search radius, 1 .. ``TRACK_MAX_RADIUS``."""
+    H, W = _luma_args(luma, 'track_init')
+    bx, R, a = _host_ints(boxes, 4, 'track_init: boxes')
+    if not 1 <= int(radius) <= TRACK_MAX_RADIUS:
+        raise ValueError(f'track_init: search radius {radius} outside 1 .. {TRACK_MAX_RADIUS}')
+    if R > 32 or (a[:, 2:] < 1).any() or (a[:, 2:] > TRACK_MAX_SIDE).any():
+        raise ValueError(f'track_init: at most 32 boxes with sides 1 .. {TRACK_MAX_SIDE}: {a.tolist()}')
+    if (a[:, :2] < 0).any() or (a[:, 0] + a[:, 2] > W).any() or (a[:, 1] + a[:, 3] > H).any():
+        raise ValueError(f'track_init: box outside the {W} x {H} image: {a.tolist()}')
+    st = TrackState(a, radius, luma.device)
+    check(_lib.lib().vfn_track_init(ptr(luma), H, W, bx, R, st.radius, ptr(st.box), ptr(st.t16), st.t16.numel(), ptr(st.acc),
+                                    st.acc.numel(), stream()), 'vfn_track_init')
+    return st
+
+
+def track_update(state, luma, box_log, ok_log, score_log, t):
+    """One frame of the tracker for all references of ``state``: search, arg-max, failure test, box move and template update on
+    the device; row ``t`` of ``box_log`` int32 [T,R,4], ``ok_log`` int32 [T,R] and ``score_log`` float32 [T,R] is written.  No host
+    synchronisation."""
+    H, W = _luma_args(luma, 'track_update')
+    R = state.R
+    T = box_log.shape[0]
+    for log, dt, shape, what in ((box_log, torch.int32, (T, R, 4), 'box_log'), (ok_log, torch.int32, (T, R), 'ok_log'),
+                                 (score_log, torch.float32, (T, R), 'score_log')):
+        if not (log.is_cuda and log.dtype == dt and tuple(log.shape) == shape and log.is_contiguous()):
+            raise ValueError(f'track_update: {what} must be a contiguous {dt} tensor of shape {shape} on the GPU')
+    if not 0 <= int(t) < T:
+        raise ValueError(f'track_update: row {t} outside logs of {T} rows')
+    check(_lib.lib().vfn_track_update(ptr(luma), H, W, state.sizes.ctypes.data_as(C.POINTER(C.c_int)), R, state.radius, ptr(state.box),
+                                      ptr(state.t16), state.t16.numel(), ptr(state.acc), state.acc.numel(), ptr(box_log), ptr(ok_log),
+                                      ptr(score_log), T, int(t), stream()), 'vfn_track_update')
+
+
+def _dev_boxes(boxes, what):
+    if not (boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.shape[0] >= 1
+            and boxes.is_contiguous()):
+        raise ValueError(f'{what}: boxes must be a contiguous int32 [R,4] tensor on the GPU')
+    return boxes.shape[0]
+
+
+def waterline_scan_dev(label, boxes, log, t, water_label=1):
+    """``waterline_scan`` under boxes int32 [R,4] = (x, y, w, h) that live on the device (a row of the tracker's box log): the key
+    point (int(x + w / 2), y + h) is computed there, and one without a row of the image below it logs -1."""
+    _lib.require_gpu(label, 'waterline_scan_dev: label')
+    if label.dtype != torch.uint8 or label.dim() != 2 or not label.is_contiguous():
+        raise ValueError('waterline_scan_dev: label must be a contiguous uint8 [H,W] tensor')
+    H, W = label.shape
+    R = _dev_boxes(boxes, 'waterline_scan_dev')
+    _log_args(log, t, R, 'waterline_scan_dev')
+    check(_lib.lib().vfn_waterline_scan_dev(ptr(label), H, W, ptr(boxes), R, int(water_label), ptr(log), log.shape[0], int(t), stream()),
+          'vfn_waterline_scan_dev')
+    return log
+
+
+def waterlevel_draw_dev(overlay, boxes, log, t):
+    """``waterlevel_draw`` under boxes int32 [R,4] that live on the device."""
+    _lib.require_gpu(overlay, 'waterlevel_draw_dev: overlay')
+    if overlay.dtype != torch.uint8 or overlay.dim() != 3 or overlay.shape[2] != 3 or not overlay.is_contiguous():
+        raise ValueError('waterlevel_draw_dev: overlay must be a contiguous uint8 [H,W,3] tensor')
+    H, W, _ = overlay.shape
+    R = _dev_boxes(boxes, 'waterlevel_draw_dev')
+    _log_args(log, t, R, 'waterlevel_draw_dev')
+    check(_lib.lib().vfn_waterlevel_draw_dev(ptr(overlay), H, W, ptr(boxes), R, ptr(log), log.shape[0], int(t), stream()),
+          'vfn_waterlevel_draw_dev')
+    return overlay

@@ -60,6 +60,10 @@ def get_args(argv=None):
                              './output/waterlevel/<name>_ref/waterlevel.csv and, with --viz, viz/.')
     parser.add_argument('--ref-bbox', type=str, default=None, help='Reference boxes, one "x y w h" row each (default: records/groundtruth/<name>/ref_bbox.txt).')
     parser.add_argument('--homo-mat', type=str, default=None, help='3 x 3 homography (default: records/groundtruth/<name>/homo_mat.txt where the test name calls for calibration).')
+    parser.add_argument('--track', choices=['off', 'on', 'auto'], default='off',
+                        help='With --waterlevel: follow the reference boxes through the clip (a translation-only correlation tracker, '
+                             'not CSRT).  auto: the reference\'s rule by test name (off for houston and LSU).')
+    parser.add_argument('--track-radius', type=int, default=16, help='Search radius of the tracker in pixels per frame (1 .. 32).')
     return parser.parse_args(argv)
 
 
@@ -536,10 +540,12 @@ def main(args, device):
             wl_dir = os.path.join('./output/waterlevel', f'{args.test_name}_ref')
             wl_viz = os.path.join(wl_dir, 'viz') if args.viz else None
             os.makedirs(wl_viz or wl_dir, exist_ok=True)
-            meter = waterlevel.WaterLevelMeter(boxes_, homo_, frames_hint=len(img_list), device=device)
+            from .est_waterlevel import use_tracking
+            meter = waterlevel.WaterLevelMeter(boxes_, homo_, frames_hint=len(img_list), device=device, track=use_tracking(args),
+                                               track_radius=getattr(args, 'track_radius', 16))
 
-            def wl_measure(label_, frame_, name_):
-                return waterlevel.measure_to_sink(meter, sink, label_, frame_ if args.viz else None, name_,
+            def wl_measure(label_, frame_, name_):               # (the sink takes the frame when it draws or tracks)
+                return waterlevel.measure_to_sink(meter, sink, label_, frame_, name_,
                                                   os.path.join(wl_viz, f'{name_}.png') if args.viz else None)
             wl_measure(torch.from_numpy(pred).to(device), ori_first_frame[0], first_name)
         staging = {}

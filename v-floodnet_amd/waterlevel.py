@@ -2,17 +2,20 @@
 on the tensors the frame loop already holds on the device.
 
 Per frame: two perspective warps (frame and label map, ``vfn_warp_perspective_*``), a column scan below each reference box
-(``vfn_waterline_scan``) and the annotated overlay (``vfn_overlay_u8`` + ``vfn_waterlevel_draw_u8``).  The scan results collect
+(``vfn_waterline_scan``) and the annotated overlay (``vfn_overlay_u8`` + ``vfn_waterlevel_draw_u8``).  With ``track=True`` the
+boxes follow the (warped) frame: ``vfn_track_*`` (a translation-only correlation tracker stated in ``include/vfn_hip.h``, not
+``cv2.TrackerCSRT``) moves them on the device and the scan and the drawing read them there.  The scan results collect
 in a device log; ``WaterLevelMeter.finish`` fetches it once per clip and runs the reference's host steps (carry-forward / NaN
 rule, Gaussian smoothing, mean over the references); ``write_csv`` writes ``waterlevel.csv`` as ``DataFrame.to_csv`` would.
 
-Not built: the interactive point / ROI pickers (a missing record file is an error that names it), the CSRT
-tracker (boxes are static, or the caller supplies them per frame through ``measure(bbox=...)``) and the matplotlib plot.
+Not built: the interactive point / ROI pickers (a missing record file is an error that names it), CSRT itself
+(the built tracker adapts neither scale nor rotation and claims no agreement with OpenCV's boxes) and the matplotlib plot.
 No OpenCV, pandas, scipy or matplotlib is imported.
 """
 import csv
 import io
 import os
+import warnings
 from datetime import datetime
 
 import numpy as np
@@ -139,6 +142,12 @@ def calibration_default(test_name):
     return not ('houston' in test_name or ('boston' not in test_name and 'LSU' in test_name))
 
 
+def tracking_default(test_name):
+    """The reference switches the box tracker on by test name (reference_tracking.py:117-140): off for ``houston`` and ``LSU``,
+    on for ``boston`` and for every name it does not know."""
+    return not ('houston' in test_name or ('boston' not in test_name and 'LSU' in test_name))
+
+
 def resolve_records(test_name, ref_bbox_path=None, homo_mat_path=None, calib=None, record_dir='./records/groundtruth'):
     """``(homo_mat or None, ref_bbox)`` for a clip: explicit files win over ``<record_dir>/<test_name>/``; ``calib`` None = on when a
     homography file is given, else the reference's default by test name (``calibration_default``)."""
@@ -152,10 +161,12 @@ def resolve_records(test_name, ref_bbox_path=None, homo_mat_path=None, calib=Non
 class WaterLevelMeter:
     """One clip's water-level measurement.  ``ref_bbox``: (x, y, w, h) per reference (static; ``measure(bbox=...)`` overrides them
     for one frame); ``homo_mat``: the 3 x 3 source -> destination homography, or None for no calibration; ``frames_hint``: rows
-    the device log starts with (it doubles when they run out).  All ``measure`` calls of a clip belong on one stream."""
+    the device log starts with (it doubles when they run out).  All ``measure`` calls of a clip belong on one stream.
+    ``track``: the boxes follow the frame (``ops.track_update``, search radius ``track_radius``): ``measure`` then needs the frame,
+    and ``finish`` leaves ``box_log`` int [T][R][4], ``track_ok`` bool [T][R] and ``track_score`` float32 [T][R]."""
 
     def __init__(self, ref_bbox, homo_mat=None, frames_hint=256, device=None, water_label=WATER_LABEL, palette=color_palette,
-                 alpha=0.4):
+                 alpha=0.4, track=False, track_radius=16):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('WaterLevelMeter: the kernels run on the GPU; there is no CPU fallback')
@@ -166,44 +177,70 @@ class WaterLevelMeter:
         self.water_label = int(water_label)
         self.palette, self.alpha = palette, alpha
         self.log = torch.full((max(1, int(frames_hint)), self.R), -1, dtype=torch.int32, device=self.device)
+        self.track, self.track_radius, self.track_state = bool(track), int(track_radius), None
+        if self.track:
+            if not 1 <= self.track_radius <= ops.TRACK_MAX_RADIUS:
+                raise ValueError(f'WaterLevelMeter: track_radius {track_radius} outside 1 .. {ops.TRACK_MAX_RADIUS}')
+            self.track_logs = [torch.zeros((self.log.shape[0],) + tail, dtype=dt, device=self.device)
+                               for tail, dt in (((self.R, 4), torch.int32), ((self.R,), torch.int32), ((self.R,), torch.float32))]
         self.names = []
         self.t = 0
         self._stream = None
 
-    def measure(self, label_dev, frame_dev=None, name=None, bbox=None, stream=None):
-        """Enqueue one frame: the warp(s) when calibrated, the scan into the log and, with ``frame_dev`` (float32 [3,H,W] in
-        [0,1]), the overlay with boxes and lines, which is returned (RGB uint8 [H,W,3] on the device; else None).  ``label_dev``:
-        uint8 [H,W].  Runs on ``stream`` (default: the current one) and never synchronises."""
+    def measure(self, label_dev, frame_dev=None, name=None, bbox=None, stream=None, overlay=None):
+        """Enqueue one frame: the warp(s) when calibrated, the tracker's step when tracking, the scan into the log and, with
+        ``frame_dev`` (float32 [3,H,W] in [0,1]), the overlay with boxes and lines, which is returned (RGB uint8 [H,W,3] on the
+        device; else None).  ``overlay=False``: the frame is for the tracker alone.  ``label_dev``: uint8 [H,W].  Runs on
+        ``stream`` (default: the current one) and never synchronises."""
         if stream is not None:
             with torch.cuda.stream(stream):
-                return self.measure(label_dev, frame_dev, name, bbox)
+                return self.measure(label_dev, frame_dev, name, bbox, overlay=overlay)
+        if self.track and (frame_dev is None or bbox is not None):
+            raise ValueError('WaterLevelMeter.measure: a tracking meter needs frame_dev and moves the boxes itself (no bbox=)')
         cur = torch.cuda.current_stream(self.device)
         if self._stream is None or cur != self._stream:
             self._stream = cur
-            self.log.record_stream(cur)
+            for log in [self.log] + (self.track_logs if self.track else []):
+                log.record_stream(cur)
         boxes = self.boxes if bbox is None else _boxes(bbox)
         if boxes.shape[0] != self.R:
             raise ValueError(f'WaterLevelMeter.measure: {boxes.shape[0]} boxes for {self.R} references')
         kp = keypoints(boxes)
         H, W = label_dev.shape
-        if ((kp[:, 0] < 0) | (kp[:, 0] >= W) | (kp[:, 1] < 0) | (kp[:, 1] >= H)).any():      # before anything is enqueued or logged
+        if not self.track and ((kp[:, 0] < 0) | (kp[:, 0] >= W) | (kp[:, 1] < 0) | (kp[:, 1] >= H)).any():      # before anything is enqueued or logged
             raise ValueError(f'WaterLevelMeter.measure: key point outside the {W} x {H} image: {kp.tolist()}')
         if self.t >= self.log.shape[0]:
             grown = torch.full((2 * self.log.shape[0], self.R), -1, dtype=torch.int32, device=self.device)
             grown[:self.t].copy_(self.log[:self.t])          # stream-ordered behind the scans that wrote those rows
             grown.record_stream(cur)
             self.log = grown
+            if self.track:
+                for k, old in enumerate(self.track_logs):
+                    self.track_logs[k] = torch.zeros((2 * old.shape[0],) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
+                    self.track_logs[k][:self.t].copy_(old[:self.t])
+                    self.track_logs[k].record_stream(cur)
         label = label_dev.contiguous()
         frame = frame_dev.contiguous() if frame_dev is not None else None
         if self.inverse is not None:
             label = ops.warp_perspective_u8(label, None, inverse=self.inverse)
             if frame is not None:
                 frame = ops.warp_perspective_u8(frame, None, inverse=self.inverse)
-        ops.waterline_scan(label, kp, self.log, self.t, self.water_label)
+        if self.track:                               # on the frame the estimator holds: the warped one when calibrated (:169, :184)
+            luma = ops.track_luma(frame)
+            if self.track_state is None:
+                self.track_state = ops.track_init(luma, boxes, self.track_radius)
+            ops.track_update(self.track_state, luma, *self.track_logs, self.t)
+            dev_boxes = self.track_logs[0][self.t]   # the row the tracker just wrote
+            ops.waterline_scan_dev(label, dev_boxes, self.log, self.t, self.water_label)
+        else:
+            ops.waterline_scan(label, kp, self.log, self.t, self.water_label)
         ov = None
-        if frame is not None:
+        if frame is not None and (overlay is None or overlay):
             ov = ops.overlay_device(frame, label, self.palette, self.alpha)
-            ops.waterlevel_draw(ov, boxes, self.log, self.t)
+            if self.track:
+                ops.waterlevel_draw_dev(ov, dev_boxes, self.log, self.t)
+            else:
+                ops.waterlevel_draw(ov, boxes, self.log, self.t)
         self.names.append(str(self.t) if name is None else str(name))
         self.t += 1
         return ov
@@ -221,6 +258,12 @@ class WaterLevelMeter:
         for r in range(self.R):
             levels[:, r] = smooth(levels[:, r])
         self.result = (list(self.names), levels, nanmean_rows(levels))
+        if self.track:                               # the tracker's logs come back with the clip, so its warnings (:188) do too
+            with torch.cuda.stream(self._stream) if self._stream is not None else torch.cuda.device(self.device):
+                box, ok, score = (log[:self.t].cpu().numpy() for log in self.track_logs)
+            self.box_log, self.track_ok, self.track_score = box, ok.astype(bool), score
+            for t in np.flatnonzero(~self.track_ok.all(axis=1)):
+                warnings.warn(f'Tracker failed at frame {self.names[t]}.')
         return self.result
 
     def write_csv(self, path):
@@ -239,9 +282,10 @@ def measure_to_sink(meter, sink, label_dev, frame_dev, name, viz_path=None):
     done = torch.cuda.Event()
     with torch.cuda.stream(sink.stream):
         sink.stream.wait_event(ready)
-        ov = meter.measure(label_dev, frame_dev if viz_path else None, name)
+        wants_frame = bool(viz_path) or meter.track
+        ov = meter.measure(label_dev, frame_dev if wants_frame else None, name, overlay=bool(viz_path))
         label_dev.record_stream(sink.stream)
-        if frame_dev is not None and viz_path:
+        if frame_dev is not None and wants_frame:
             frame_dev.record_stream(sink.stream)
         done.record()
     if ov is not None:
