@@ -27,7 +27,7 @@ extern "C" {
 /* ------------------------------------------------------------------ version
  * vfn_abi_version() == VFN_ABI_VERSION of the header the binding was written against, and
  * vfn_sizeof_desc(which) == sizeof of the binding's own struct: checked when the library is loaded. */
-#define VFN_ABI_VERSION 17
+#define VFN_ABI_VERSION 18
 enum { VFN_DESC_CONV = 0, VFN_DESC_STEM = 1, VFN_DESC_BANKSCAN = 2, VFN_DESC_MEMREAD = 3, VFN_DESC_BANK = 4, VFN_DESC_WGRAD = 5,
        VFN_DESC_REFRESH_FILTER = 6, VFN_DESC_REFRESH_EPILOGUE = 7, VFN_DESC_GATHER = 8, VFN_DESC_BANKMATCH = 9,
        VFN_DESC_TRAIN_AUG = 10 };
@@ -880,6 +880,50 @@ int vfn_train_aug_affine(const vfn_train_aug_desc* d, void* stream);
 int vfn_train_aug_resize(const vfn_train_aug_desc* d, void* stream);
 int vfn_train_aug_label_present(const unsigned char* mask, int H, int W, const int* xtab, const int* ytab, int S,
                                 unsigned char* present, void* stream);
+
+/* ------------------------------------------------------------------ image segmentation on the device (test_image_seg.py)
+ * predict_pil / predict_one (test_image_seg.py:67-124) around model.predict, for a folder of photographs of any sizes.  The
+ * arithmetic, rule by rule; no fused multiply-adds anywhere (fp contract off), f32 division correctly rounded.
+ *
+ * vfn_imgseg_resize_norm   Image.resize((w, h), Image.BILINEAR) of the decoded photograph src uint8 [H][W][3], then ToTensor
+ *     and Normalize, written into slot b of the model's input x float [B][3][h][w].  libImaging/Resample.c, 8 bits per channel:
+ *     a horizontal then a vertical pass of out = clip8((2^21 + sum k p) >> 22) with the host's tables (bounds int32 [n][2] =
+ *     (first source index, count), coefficients int32 [n][ksize] = int(+-0.5 + wt 2^22) of the normalised triangle weights
+ *     wt(t) = 1 - |t| for |t| < 1, evaluated at (source index - centre + 0.5) / max(scale, 1) over a support of max(scale, 1),
+ *     scale = source size / result size, centre = (result index + 0.5) scale; the host builds them in double in Pillow's
+ *     operation order).  The horizontal result is rounded to uint8 (hpass [H][w][3] scratch).  A pass whose size does not
+ *     change is skipped as Pillow skips it: W == w takes no kx tables and no hpass, H == h no ky tables.  Then, per channel c,
+ *     x = (float(u8) / 255.0f - mean[c]) / std[c] in f32: the bits of torch's (t.float().div(255) - mean) / std.
+ *     1 <= H, W <= VFN_IMGSEG_MAX_SIDE, 1 <= h, w <= VFN_IMGSEG_MAX_OUT, 0 <= b < B.  One or two launches.
+ * vfn_imgseg_upsample_round   the probability map prob float [h][w] enlarged (or reduced) to [H][W] bilinearly with
+ *     align_corners = False and no antialiasing, rounded to a label: labels uint8 [H][W].  As a definition, all in f32:
+ *     sy = float(h) / float(H); fy = max(sy * (float(y) + 0.5f) - 0.5f, 0); y0 = (int) fy; y1 = y0 + (y0 < h - 1);
+ *     wy1 = fy - float(y0); wy0 = 1.0f - wy1; likewise for x; v = wy0 * (wx0 * p[y0][x0] + wx1 * p[y0][x1]) +
+ *     wy1 * (wx0 * p[y1][x0] + wx1 * p[y1][x1]) (four products, the two inner sums, two products, the outer sum);
+ *     label = rint(min(max(v, 0), 255)), halves to even (a NaN becomes 0).  This is F.interpolate(..., mode='bilinear',
+ *     align_corners=False).round() up to the last bits of v (torch's CPU kernel orders its operations differently): a label
+ *     can differ only where v is within 2^-13 of 0.5 (h, w <= 512, values in [0, 1]).  1 <= h, w <= VFN_IMGSEG_MAX_OUT,
+ *     1 <= H, W <= VFN_IMGSEG_MAX_SIDE.  One launch.
+ *
+ * LinkNet at batch B (linknet.LinknetB4.predict_batch, B > 1): the squeeze-excite gate of image b scales the rows of image b of the
+ * depthwise output in place, in front of an ordinary batched project convolution (at B == 1 the gate scales the filter
+ * matrix's columns instead, vfn_ln_scale_cols_f32; the two differ in the last bits).  x float [B][M][ld], M pixels per image.
+ * vfn_ln_colsum_batch_f32    part [B][nb][C]: chunk j of image b sums the rows j R .. min((j + 1) R, M) - 1, R = ceil(M / nb),
+ *                            of each channel (16 interleaved running sums per chunk, then a tree); C % 4 == 0, 1 <= nb <= 1024
+ * vfn_ln_se_gate_batch_f32   per image: sum_px[c] = part[b][0][c] + part[b][1][c] + ... in that order, then vfn_ln_se_gate_f32's
+ *                            rule; gate [B][Cpad], gate[b][C..Cpad-1] = 0; part's channel stride is Cpad; Cpad <= 4096, sq <= 256
+ * vfn_ln_scale_rows_f32      x[b][m][c] *= gate[b][c] in place, c < C (C % 4 == 0, ld % 4 == 0, gate's stride C)
+ * Every entry returns VFN_ERR_ARG, and launches nothing, for a null pointer it needs or a size outside these ranges. */
+#define VFN_IMGSEG_MAX_SIDE 8192
+#define VFN_IMGSEG_MAX_OUT 4096
+int vfn_imgseg_resize_norm(const unsigned char* src, int H, int W, unsigned char* hpass, const int* kx_bounds, const int* kx,
+                           int ksize_x, const int* ky_bounds, const int* ky, int ksize_y, float* x, int B, int b, int h, int w,
+                           const float* mean, const float* std, void* stream);
+int vfn_imgseg_upsample_round(const float* prob, int h, int w, unsigned char* labels, int H, int W, void* stream);
+int vfn_ln_colsum_batch_f32(const float* x, int B, int M, int C, int ld, float* part, int nb, void* stream);
+int vfn_ln_se_gate_batch_f32(const float* part, int nb, float inv_hw, const float* w1, const float* b1, const float* w2,
+                             const float* b2, float* gate, int B, int C, int sq, int Cpad, void* stream);
+int vfn_ln_scale_rows_f32(float* x, const float* gate, int B, int M, int C, int ld, void* stream);
 
 #ifdef __cplusplus
 }

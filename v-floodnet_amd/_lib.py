@@ -119,7 +119,7 @@ class TrainAugDesc(C.Structure):
                 ('frame', TrainAugFrame * TRAIN_AUG_MAX_T)]
 
 
-ABI_VERSION = 17         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
+ABI_VERSION = 18         # include/vfn_hip.h VFN_ABI_VERSION; csrc/abi.hip
 DESC_IDS = {0: ConvDesc, 1: StemDesc, 2: BankScanDesc, 3: MemReadDesc, 4: BankDesc, 5: WgradDesc, 6: RefreshFilter, 7: RefreshEpilogue, 8: GatherEntry, 9: BankMatchDesc, 10: TrainAugDesc}     # vfn_sizeof_desc(which)
 
 
@@ -269,6 +269,11 @@ SIGNATURES = {
     'vfn_waterline_scan_dev': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p],
     'vfn_waterlevel_draw_dev': [_p, _i, _i, _p, _i, _p, _i, _i, _p],
     'vfn_train_aug_label_present': [_p, _i, _i, _p, _p, _i, _p, _p],
+    'vfn_imgseg_resize_norm': [_p, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _p],
+    'vfn_imgseg_upsample_round': [_p, _i, _i, _p, _i, _i, _p],
+    'vfn_ln_colsum_batch_f32': [_p, _i, _i, _i, _i, _p, _i, _p],
+    'vfn_ln_se_gate_batch_f32': [_p, _i, _f, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'vfn_ln_scale_rows_f32': [_p, _p, _i, _i, _i, _i, _p],
 }
 # every symbol include/vfn_hip.h declares (checked by tests/test_abi.py)
 ALL_SYMBOLS = sorted(list(SIGNATURES) + [

@@ -6,6 +6,7 @@
 // 13: vfn_bankmatch_desc, vfn_bank_match_certified, vfn_bank_refresh_lp_keys
 // 15: vfn_conv_cfg_modes
 // 16: vfn_train_aug_desc, vfn_train_aug_* (training clips)
+// 18: vfn_imgseg_*, vfn_ln_colsum_batch_f32, vfn_ln_se_gate_batch_f32, vfn_ln_scale_rows_f32 (image segmentation on the device)
 extern "C" int vfn_abi_version(void) { return VFN_ABI_VERSION; }
 
 // sizeof of every descriptor as THIS library was compiled: a binding whose struct layout drifted fails its

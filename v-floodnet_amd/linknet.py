@@ -4,6 +4,7 @@
 
     model = LinknetB4.from_checkpoint('records/link_efficientb4_model.pth', device)   # or LinknetB4(device); load_state_dict(sd)
     prob = model.predict(x)            # x f32 [1,3,416,416] ImageNet-normalised -> f32 [1,1,416,416] in [0,1]  (the smp API)
+    prob = model.predict_batch(xb)     # xb f32 [B,3,416,416]: the batch as one launch list (image_seg.ImageSegRunner)
 
 The module is a parameter container with the state-dict names of segmentation_models_pytorch 0.2.0 / efficientnet-pytorch 0.6.3
 (``encoder._blocks.7._se_reduce.weight``, ``decoder.blocks.2.block.1.0.bias``, ``segmentation_head.0.weight`` ...), so the state dict
@@ -144,7 +145,7 @@ class LinknetB4(nn.Module):
         self.decoder = _Decoder()
         self.segmentation_head = nn.Sequential(nn.Conv2d(32, 1, 1), nn.Identity(), nn.Identity())
         self._packed = None
-        self._graphs, self._graph_runs = {}, {}        # (H, W, logits) -> (captured graph, static input, static output) / eager calls so far
+        self._graphs, self._graph_runs = {}, {}        # (H, W, logits), or (B, H, W, logits) for B > 1 -> (captured graph, static input, static output) / eager calls so far
         if device is not None:
             self.to(device)
         self.eval()
@@ -252,20 +253,32 @@ class LinknetB4(nn.Module):
 
     @torch.no_grad()
     def predict(self, x, logits=False):
-        """x f32 [1,3,H,W] (H, W multiples of 32) on the GPU -> probabilities f32 [1,1,H,W] (``smp`` ``model.predict``)."""
+        """x f32 [N,3,H,W] (H, W multiples of 32) on the GPU -> probabilities f32 [N,1,H,W] (``smp`` ``model.predict``).  N > 1: the
+        single-image results, bit for bit (image by image; ``predict_batch`` runs a batch as one launch list)."""
+        _lib.require_gpu(x, 'x')
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f'expected a normalised RGB batch [N,3,H,W], got {tuple(x.shape)}')
+        if x.shape[0] != 1:
+            return torch.cat([self.predict(x[i:i + 1], logits) for i in range(x.shape[0])], 0)
+        return self.predict_batch(x, logits)
+
+    @torch.no_grad()
+    def predict_batch(self, x, logits=False):
+        """x f32 [B,3,H,W] -> f32 [B,1,H,W] as ONE launch list whose length does not depend on B (``_predict_eager``: per-image
+        squeeze-excite gates applied to the rows of the depthwise output).  Per image within the float64 tolerance of the oracle,
+        and so of ``predict``, not its bits (the gate multiplies activations instead of filter columns, and the larger GEMMs pick
+        other tiles); B == 1 is ``predict``."""
         _lib.require_gpu(x, 'x')
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f'expected a normalised RGB batch [N,3,H,W], got {tuple(x.shape)}')
         if x.shape[2] % 32 or x.shape[3] % 32:
             raise RuntimeError(f'input height and width must be divisible by 32 (5 stride-2 stages), got {tuple(x.shape[2:])}')
-        if x.shape[0] != 1:
-            return torch.cat([self.predict(x[i:i + 1], logits) for i in range(x.shape[0])], 0)
         P = self._packed or self._pack()
         # ≈ 230 launches of a few microseconds each, paced by the host (3.3 ms per 416 x 416 call): from the third call at one input size
-        # on they are ONE captured HIP graph per (size, logits) -- static input / output buffers, the intermediates in the graph's pool
+        # on they are ONE captured HIP graph per (batch, size, logits) -- static input / output buffers, the intermediates in the graph's pool
         # (round 5; VFN_GRAPHS=0 or a failed capture: the launch-by-launch path below)
         from .engine import _GRAPHS
-        key = (x.shape[2], x.shape[3], bool(logits))
+        key = (x.shape[2], x.shape[3], bool(logits)) if x.shape[0] == 1 else (x.shape[0], x.shape[2], x.shape[3], bool(logits))
         g = self._graphs.get(key) if _GRAPHS else None
         if g is not None:
             g[1].copy_(x)
@@ -293,13 +306,14 @@ class LinknetB4(nn.Module):
                     self._graph_runs[key] = -10 ** 9
         return self._predict_eager(P, x, logits)
 
-    def _predict_eager(self, P, x, logits, taps=None):
-        """The launches of one frame.  ``taps``: a list that receives the stem output, the four stage features and the five decoder
-        block outputs (after their skip adds) as the NHWC, channel-padded tensors the kernels wrote -- no copy (tests)."""
+    def _predict_eager(self, P, x, logits, taps=None, gates=None):
+        """The launches of one batch.  ``taps``: a list that receives the stem output, the four stage features and the five decoder
+        block outputs (after their skip adds) as the NHWC, channel-padded tensors the kernels wrote -- no copy (tests).  ``gates``
+        (B > 1): a list that receives every block's squeeze-excite gates f32 [B, channels padded]."""
         L = _lib.lib()
         dev = P['dev']
         x = x.float().contiguous()
-        N, H, Wd = 1, x.shape[2], x.shape[3]
+        N, H, Wd = x.shape[0], x.shape[2], x.shape[3]
         f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
         h, w = H // 2, Wd // 2
         cur = f(N, h, w, 64)
@@ -319,15 +333,29 @@ class LinknetB4(nn.Module):
             check(L.vfn_ln_dwconv_f32(ptr(ex), ptr(q['dw_w']), ptr(q['dw_sc']), ptr(q['dw_sh']), ptr(dwo), N, h, w, q['oup_p'],
                                       q['oup_p'], q['oup_p'], q['k'], q['s'], q['pad_b'], ho, wo, int(q['e'] != 1), stream()),
                   'vfn_ln_dwconv_f32')
-            M = N * ho * wo
-            sums, part, gate = f(q['oup_p']), f(NB * q['oup_p']), f(q['oup_p'])
-            check(L.vfn_colsum_f32(ptr(dwo), M, q['oup_p'], q['oup_p'], ptr(part), NB, ptr(sums), stream()), 'vfn_colsum_f32')
-            check(L.vfn_ln_se_gate_f32(ptr(sums), 1.0 / M, ptr(q['se_w1']), ptr(q['se_b1']), ptr(q['se_w2']), ptr(q['se_b2']), ptr(gate),
-                                       q['oup'], q['sq'], q['oup_p'], stream()), 'vfn_ln_se_gate_f32')
-            # se_w1 is [sq][oup] over the UNPADDED channels while the sums are padded: gather is by index < oup, same layout
-            wg = torch.empty_like(q['proj_w'])
-            check(L.vfn_ln_scale_cols_f32(ptr(q['proj_w']), ptr(gate), ptr(wg), q['proj_w'].shape[0], q['oup_p'], stream()),
-                  'vfn_ln_scale_cols_f32')
+            M = ho * wo
+            if N == 1:
+                sums, part, gate = f(q['oup_p']), f(NB * q['oup_p']), f(q['oup_p'])
+                check(L.vfn_colsum_f32(ptr(dwo), M, q['oup_p'], q['oup_p'], ptr(part), NB, ptr(sums), stream()), 'vfn_colsum_f32')
+                check(L.vfn_ln_se_gate_f32(ptr(sums), 1.0 / M, ptr(q['se_w1']), ptr(q['se_b1']), ptr(q['se_w2']), ptr(q['se_b2']), ptr(gate),
+                                           q['oup'], q['sq'], q['oup_p'], stream()), 'vfn_ln_se_gate_f32')
+                # se_w1 is [sq][oup] over the UNPADDED channels while the sums are padded: gather is by index < oup, same layout
+                wg = torch.empty_like(q['proj_w'])
+                check(L.vfn_ln_scale_cols_f32(ptr(q['proj_w']), ptr(gate), ptr(wg), q['proj_w'].shape[0], q['oup_p'], stream()),
+                      'vfn_ln_scale_cols_f32')
+            else:
+                # a batch: image b's gate cannot ride in the shared filter matrix, and one filter bank per image (w_batch_rows) only
+                # fits where an image's rows are a multiple of the tile height -- so gate b scales the rows of image b of the depthwise
+                # output in place, in front of an ordinary batched project convolution; the same route for every block
+                nb = max(1, min(64, M // 64))
+                part, gate = f(N * nb * q['oup_p']), f(N, q['oup_p'])
+                check(L.vfn_ln_colsum_batch_f32(ptr(dwo), N, M, q['oup_p'], q['oup_p'], ptr(part), nb, stream()), 'vfn_ln_colsum_batch_f32')
+                check(L.vfn_ln_se_gate_batch_f32(ptr(part), nb, 1.0 / M, ptr(q['se_w1']), ptr(q['se_b1']), ptr(q['se_w2']), ptr(q['se_b2']),
+                                                 ptr(gate), N, q['oup'], q['sq'], q['oup_p'], stream()), 'vfn_ln_se_gate_batch_f32')
+                check(L.vfn_ln_scale_rows_f32(ptr(dwo), ptr(gate), N, M, q['oup_p'], q['oup_p'], stream()), 'vfn_ln_scale_rows_f32')
+                wg = q['proj_w']
+                if gates is not None:
+                    gates.append(gate)
             out = f(N, ho, wo, q['cout_p'])
             skip = inp if (q['s'] == 1 and q['cin'] == q['cout']) else None
             self._conv(P, dwo, wg, q['cout_p'], 1, 0, out, q['proj_sc'], q['proj_sh'], N, ho, wo, res=skip)

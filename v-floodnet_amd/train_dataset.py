@@ -52,15 +52,16 @@ def inverse_affine_matrix(W, H, angle, translate, scale, shear_x):
     return m
 
 
-def resize_tables(n_in, n_out):
-    """Pillow's ``precompute_coeffs`` and ``normalize_coeffs_8bpc`` (libImaging/Resample.c) for the bicubic filter, one axis:
+def resize_tables(n_in, n_out, filt='bicubic'):
+    """Pillow's ``precompute_coeffs`` and ``normalize_coeffs_8bpc`` (libImaging/Resample.c) for the bicubic filter (or, with
+    ``filt='bilinear'``, the triangle filter of support 1: ``image_seg``), one axis:
     (bounds int32 [n_out, 2] = (first source index, count), coefficients int32 [n_out, ksize]).  Vectorised, but every
     number goes through the same double-precision operations in the same order as in the C loop (the running sum of the
     weights is a sequential ``cumsum``)."""
     scale = fscale = n_in / n_out
     if fscale < 1.0:
         fscale = 1.0
-    support = 2.0 * fscale
+    support = (2.0 if filt == 'bicubic' else 1.0) * fscale
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / fscale
     center = (np.arange(n_out) + 0.5) * scale
@@ -70,8 +71,11 @@ def resize_tables(n_in, n_out):
     valid = x < xmax[:, None]
     arg = np.abs(((x + xmin[:, None]) - center[:, None] + 0.5) * ss)
     a = -0.5
-    w = np.where(arg < 1.0, ((a + 2.0) * arg - (a + 3.0)) * arg * arg + 1,
-                 np.where(arg < 2.0, (((arg - 5) * arg + 8) * arg - 4) * a, 0.0))
+    if filt == 'bicubic':
+        w = np.where(arg < 1.0, ((a + 2.0) * arg - (a + 3.0)) * arg * arg + 1,
+                     np.where(arg < 2.0, (((arg - 5) * arg + 8) * arg - 4) * a, 0.0))
+    else:
+        w = np.where(arg < 1.0, 1.0 - arg, 0.0)
     w = np.where(valid, w, 0.0)
     ww = np.cumsum(w, axis=1)[:, -1:]
     w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
