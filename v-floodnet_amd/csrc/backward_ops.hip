@@ -993,11 +993,14 @@ void maxpool3x3s2_bwd4_kernel(const float* __restrict__ x, const float* __restri
 // ------------------------------------------------------------------ memory read, backwards (training: the bank is one frame)
 // P[b][q] = softmax over b of scale * S[b][q] (AFB_URR.py:144-145).  64 query columns per workgroup, the bank rows dealt to
 // SM_R row groups (round 3 walked all B rows three times on ONE thread per column: 340 us at B = Q = 625); the groups' maxima
-// and sums meet through LDS in group order (deterministic).
+// and sums meet through LDS in group order (deterministic).  The normaliser is summed in double and every P is ONE rounding of
+// e * (1 / l): a column of P sums to 1 within one float rounding (a float running sum left l, and the column sum with it, up to
+// 3e-7 off at B = 100; tests/test_backward_kernels_gpu.py).
 constexpr int SM_R = 16;
 __global__ __launch_bounds__(64 * SM_R)
 void softmax_cols_kernel(const float* __restrict__ S, int B, int Q, int ld, float scale, float* __restrict__ P) {
     __shared__ float red[SM_R][64];
+    __shared__ double redl[SM_R][64];
     const int cx = threadIdx.x & 63, rgp = threadIdx.x >> 6;
     const int q = blockIdx.x * 64 + cx;
     const bool ok = q < Q;
@@ -1010,16 +1013,17 @@ void softmax_cols_kernel(const float* __restrict__ S, int B, int Q, int ld, floa
 #pragma unroll
     for (int g = 1; g < SM_R; ++g) m = fmaxf(m, red[g][cx]);
     __syncthreads();
-    float l = 0.f;
+    double l = 0.0;
     if (ok)
-        for (int b = rgp; b < B; b += SM_R) l += expf(S[(size_t)b * ld + q] * scale - m);
-    red[rgp][cx] = l;
+        for (int b = rgp; b < B; b += SM_R) l += (double)expf(S[(size_t)b * ld + q] * scale - m);
+    redl[rgp][cx] = l;
     __syncthreads();
-    l = 0.f;
+    l = 0.0;
 #pragma unroll
-    for (int g = 0; g < SM_R; ++g) l += red[g][cx];
+    for (int g = 0; g < SM_R; ++g) l += redl[g][cx];
+    const double inv = ok ? 1.0 / l : 0.0;
     if (ok)
-        for (int b = rgp; b < B; b += SM_R) P[(size_t)b * ld + q] = expf(S[(size_t)b * ld + q] * scale - m) / l;
+        for (int b = rgp; b < B; b += SM_R) P[(size_t)b * ld + q] = (float)((double)expf(S[(size_t)b * ld + q] * scale - m) * inv);
 }
 // dS[b][q] = scale * P (dP - sum_b' P dP)
 __global__ __launch_bounds__(64 * SM_R)
