@@ -96,3 +96,120 @@ def test_product_never_imports_the_oracle():
         if fn.endswith('.py'):
             src = open(os.path.join(pkg, fn)).read()
             assert 'import oracle' not in src and 'from oracle' not in src, fn
+
+
+# ---------------------------------------------------------------------------------------------- the binding is derived from the header
+def _hipcc():
+    """The compiler of v-floodnet_amd/csrc/Makefile (HIPCC ?= hipcc)."""
+    import shutil
+    return shutil.which(os.environ.get('HIPCC', 'hipcc')) or shutil.which('/opt/rocm/bin/hipcc')
+
+
+def _c_type(t):
+    """The C spelling of a derived field type, or None for a pointer (every pointer field travels as void*)."""
+    import ctypes as C
+    from vfloodnet_amd import _lib
+    if hasattr(t, '_length_'):
+        return f'{_c_type(t._type_)}[{t._length_}]'
+    names = {C.c_int: 'int', C.c_float: 'float', C.c_double: 'double', C.c_longlong: 'long long', C.c_void_p: None}
+    return names[t] if t in names else {c: n for n, c in _lib.STRUCTS.items()}[t]
+
+
+def test_compiler_agrees_with_the_derived_structs(tmp_path):
+    """One translation unit of static_asserts -- sizeof of every struct; offset, size and C type of every field as the parser derived
+    them -- compiled host-only (syntax check: no device code, nothing runs) against include/vfn_hip.h."""
+    import ctypes as C
+    import subprocess
+    import vfloodnet_amd  # noqa: F401
+    from vfloodnet_amd import _lib
+    cc = _hipcc()
+    if cc is None:
+        pytest.skip('no hipcc on this machine')
+    c_name = {py: c for c, py in _lib._RENAMED.items()}
+    lines = ['#include <cstddef>', '#include <type_traits>', '#include "vfn_hip.h"']
+    assert len(_lib.STRUCTS) == 12
+    for sname, cls in _lib.STRUCTS.items():
+        lines.append(f'static_assert(sizeof({sname}) == {C.sizeof(cls)}, "sizeof {sname}");')
+        for fname, ftype in cls._fields_:
+            f, d, ct = c_name.get(fname, fname), getattr(cls, fname), _c_type(ftype)
+            lines.append(f'static_assert(offsetof({sname}, {f}) == {d.offset} && sizeof((({sname}*)0)->{f}) == {d.size}, "{sname}.{f}");')
+            kind = f'std::is_same<decltype({sname}::{f}), {ct}>' if ct else f'std::is_pointer<decltype({sname}::{f})>'
+            lines.append(f'static_assert({kind}::value, "type of {sname}.{f}");')
+    src = tmp_path / 'abi_layout.cpp'
+    src.write_text('\n'.join(lines) + '\n')
+    r = subprocess.run([cc, '-x', 'c++', '-std=c++11', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_prototypes_are_derived_by_the_type_rule():
+    import ctypes as C
+    import vfloodnet_amd  # noqa: F401
+    from vfloodnet_amd import _lib
+    S = _lib.SIGNATURES
+    i, p, ll, d = C.c_int, C.c_void_p, C.c_longlong, C.c_double
+    assert sorted(S) == declared_symbols() and len(S) == 111
+    assert S['vfn_abi_version'] == []
+    assert S['vfn_conv_cfg_name'] == [i, C.c_char_p, i]
+    assert S['vfn_conv2d_nhwc_f32'] == [C.POINTER(_lib.ConvDesc), i, p]
+    assert S['vfn_conv1x1_persistent_f32'] == [C.POINTER(_lib.ConvDesc), i, i, p]
+    assert S['vfn_refresh_filters_f32'] == [p, i, i, p]                                      # table_dev: a struct pointer named *_dev
+    assert S['vfn_refresh_epilogues_f32'][0] is p and S['vfn_gather_strided_f32'][0] is p
+    assert S['vfn_adamw_f32'] == [p, p, p, p, ll, d, d, d, d, d, i, p]
+    assert S['vfn_winograd_output_f32'] == [p, i, i, i, i, i, p, p, p, i, i, i, p, i, p]     # a prototype that spans lines
+    assert S['vfn_scatter_mean_checked_f32'] == [p, ll, ll, p, ll, i, p, ll, ll, i, ll, p, p]   # const long long* -> void*
+    assert S['vfn_jpeg_idct_u8'] == [p, p, p, i, i, i, p]                                    # short*, unsigned short* -> void*
+    assert S['vfn_softmax_cols_f32'] == [p, i, i, i, C.c_float, p, p]
+    assert S['vfn_bank_refresh_norms'] == [C.POINTER(_lib.BankDesc), p, p, p, p]
+    assert C.POINTER(_lib.ConvDesc) is C.POINTER(_lib.STRUCTS['vfn_conv_desc']) and _lib.ConvDesc._fields_[0][0] == 'inp'
+    assert _lib.TrainAugDesc.frame.size == 16 * C.sizeof(_lib.TrainAugFrame) and _lib.TrainAugDesc.obj_list.size == 40
+
+
+def test_parser_refuses_what_it_does_not_understand():
+    import vfloodnet_amd  # noqa: F401
+    from vfloodnet_amd._lib import parse_header
+    ok = 'typedef struct vfn_s { const float* in; int n[VFN_N - 1]; } vfn_s;\nint vfn_f(const vfn_s* d, const vfn_s* t_dev, void* stream);\n'
+    defines, enums, structs, protos = parse_header('#define VFN_N (2 * 2)\nenum { VFN_A = 3, VFN_B };\n' + ok)
+    assert defines == {'VFN_N': 4} and enums == {'VFN_A': 3, 'VFN_B': 4} and [f[0] for f in structs['vfn_s']._fields_] == ['inp', 'n']
+    assert structs['vfn_s'].n.size == 12 and protos['vfn_f'][1:] == [__import__('ctypes').c_void_p] * 2
+    for bad, names in (('typedef struct { size_t n; } vfn_s;', 'size_t'),                    # an unknown base type
+                       ('typedef struct { int n[VFN_NOT_DEFINED]; } vfn_s;', 'VFN_NOT_DEFINED'),   # a bound that does not evaluate
+                       ('#define VFN_N 4\n' + ok + 'int vfn_g(vfn_s d);', 'vfn_g'),            # a struct by value
+                       ('#define VFN_N 4\n' + ok + 'int vfn_g(size_t n);', 'vfn_g'),
+                       ('#define VFN_N 4\n' + ok + 'int vfn_g(int n)', 'vfn_g'),               # unbalanced: no terminator
+                       ('typedef struct { int n; vfn_s;', 'int n'),
+                       ('int vfn_g(int n);\n}', 'unbalanced'),
+                       ('float vfn_g(int n);', 'vfn_g'),                                       # every entry point returns int
+                       ('int vfn_g(int n);\nint vfn_g(int n);', 'vfn_g'),
+                       ('#define VFN_F(x) 1', 'VFN_F'), ('#include <stddef.h>', 'stddef')):
+        with pytest.raises(RuntimeError, match=names):
+            parse_header(bad)
+
+
+def test_constants_come_from_the_header():
+    import vfloodnet_amd  # noqa: F401
+    from vfloodnet_amd import _lib, ops, feature_bank, backward
+    hdr = open(os.path.join(ROOT, 'include', 'vfn_hip.h')).read()
+
+    def define(name):
+        return eval(re.search(r'#define ' + name + r' ([\d\s()*]+)', hdr).group(1))
+
+    assert _lib.ABI_VERSION == define('VFN_ABI_VERSION') == 18
+    assert ops.SK_WS_FLOATS == define('VFN_CONV_SK_WS_FLOATS') == 16 * 1024 * 1024
+    assert ops.SK_MAX_TILES == define('VFN_CONV_SK_MAX_TILES') == 16384
+    assert feature_bank.MAX_HW == define('VFN_BANK_MAX_HW') == 32768
+    assert (_lib.TRAIN_AUG_MAX_T, _lib.TRAIN_AUG_MAX_SIDE, _lib.TRAIN_AUG_MAX_OUT, _lib.TRAIN_AUG_MAX_OBJ) == tuple(
+        define('VFN_TRAIN_AUG_MAX_' + k) for k in ('T', 'SIDE', 'OUT', 'OBJ')) == (16, 8192, 4096, 11)
+    assert backward.COLSUM_COUNTERS == define('VFN_COLSUM_COUNTERS') == 64
+    src = open(os.path.join(ROOT, 'v-floodnet_amd', 'backward.py')).read()                    # every ticket buffer has that length
+    assert len(re.findall(r'self\._ticket\w* = torch\.zeros\(COLSUM_COUNTERS, dtype=torch\.int32', src)) == len(re.findall(r'self\._ticket\w* = ', src)) == 6
+    assert {_lib.DESC_IDS[_lib.ENUMS[k]].__name__ for k in _lib.ENUMS} == set(_lib.STRUCTS) - {'vfn_train_aug_frame'}
+
+
+def test_a_declared_symbol_the_library_lacks_is_named(monkeypatch):
+    import vfloodnet_amd  # noqa: F401
+    from vfloodnet_amd import _lib
+    monkeypatch.setattr(_lib, '_lib', None)
+    monkeypatch.setitem(_lib.SIGNATURES, 'vfn_not_in_the_library', [])
+    with pytest.raises(RuntimeError, match='vfn_not_in_the_library'):
+        _lib.lib()

@@ -27,6 +27,7 @@ from .refresh import DGRAD
 from .engine import choose_cfg, apply_choice, DK, DV
 
 
+COLSUM_COUNTERS = _lib.DEFINES['VFN_COLSUM_COUNTERS']      # ints of an arrival-counter buffer of the one-launch column sums
 _IMPLICIT_WGRAD = __import__('os').environ.get('VFN_IMPLICIT_WGRAD', '1') == '1'      # 0: the round-3 path (transposed operands)
 _SIDE_WGRAD = __import__('os').environ.get('VFN_SIDE_WGRAD', '1') == '1'              # 0: weight gradients on the main stream
 _SIDE_PRIORITY = int(__import__('os').environ.get('VFN_SIDE_PRIORITY', 0))               # -1: the side stream's kernels are dispatched first
@@ -77,8 +78,8 @@ class DecoderBackward:
         self._filters('local_convFM.loc', wl, 64, 64)
         self._filters('local_pred2', d.local_pred2.weight, cout_ld=32)
         self._scratch = {}
-        self._ticket = torch.zeros(64, dtype=torch.int32, device=dev)      # arrival counters (VFN_COLSUM_COUNTERS) of the one-launch column sums, zero at rest
-        self._ticket_main = torch.zeros(64, dtype=torch.int32, device=dev) # ... of the column sums that stay on the main stream (unnamed / fallback paths)
+        self._ticket = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev)      # arrival counters (VFN_COLSUM_COUNTERS) of the one-launch column sums, zero at rest
+        self._ticket_main = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev) # ... of the column sums that stay on the main stream (unnamed / fallback paths)
         self.sink = None                                   # ModelBackward: weight gradients accumulate there, in the kernel
 
     def _filters(self, name, weight, cin_off=0, cin=None, cout_ld=0):
@@ -446,7 +447,7 @@ class ModelBackward:
             reg.add_filter(c.weight, self.cb['keyval'].wp, DGRAD, dst_ld=9 * wkv.shape[0], dst_col0=col, cout_ld=wkv.shape[0])
             col += c.weight.shape[0]
         self._grads = {}
-        self._ticket = torch.zeros(64, dtype=torch.int32, device=dev)      # arrival counters (VFN_COLSUM_COUNTERS) of the one-launch column sums, zero at rest
+        self._ticket = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev)      # arrival counters (VFN_COLSUM_COUNTERS) of the one-launch column sums, zero at rest
         # convolution weight gradients accumulate IN THE KERNEL (vfn_conv_wgrad_f32, accumulate = 1) in the packed filter layout
         # [Cout][kh][kw][Cin]; ``grads`` hands them out as [Cout,Cin,kh,kw] views -- no torch add / copy per sample and layer
         self._packed = {}            # name -> (buffer [cout, k*k*cin], cout, k, cin)
@@ -470,12 +471,12 @@ class ModelBackward:
         # which is idle during a backward pass)
         self.side3 = independent_stream(dev, beside=[self.side, self.side2], priority=_SIDE_PRIORITY) if (_SIDE_WGRAD and _SIDE2 and _SIDE3) else None
         self._pending2, self._pending3, self._lane = [], [], 0        # lane 0: decoder + KeyValue, 1: memory encoder, 2: query encoder
-        self._ticket2 = torch.zeros(64, dtype=torch.int32, device=dev)
-        self._ticket3 = torch.zeros(64, dtype=torch.int32, device=dev)
+        self._ticket2 = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev)
+        self._ticket3 = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev)
         self._pad = {}               # zero-padded operand images of the memory read's small GEMMs (_gemm_nt)
         self._query_grads = {}       # slot -> gradients entering the memory read / the query encoder (batched samples: finish_query)
         self._batch_fb = None        # ... and the bank they were segmented against
-        self._ticket_main = torch.zeros(64, dtype=torch.int32, device=dev)  # (the column sums that stay on the main stream)
+        self._ticket_main = torch.zeros(COLSUM_COUNTERS, dtype=torch.int32, device=dev)  # (the column sums that stay on the main stream)
 
     def reset(self):
         """Forget the gradients of the previous step (their tensors belong to whoever took them from ``grads``)."""

@@ -9,8 +9,9 @@
 // 18: vfn_imgseg_*, vfn_ln_colsum_batch_f32, vfn_ln_se_gate_batch_f32, vfn_ln_scale_rows_f32 (image segmentation on the device)
 extern "C" int vfn_abi_version(void) { return VFN_ABI_VERSION; }
 
-// sizeof of every descriptor as THIS library was compiled: a binding whose struct layout drifted fails its
-// load-time check (v-floodnet_amd/_lib.py, tests/test_abi.py) instead of reading past the caller's struct
+// sizeof of every descriptor as THIS library was compiled: a binding that read another header than this library's
+// (v-floodnet_amd/_lib.py derives its structs from include/vfn_hip.h) fails its load-time check instead of
+// reading past the caller's struct
 extern "C" int vfn_sizeof_desc(int which) {
     switch (which) {
         case VFN_DESC_CONV: return (int)sizeof(vfn_conv_desc);

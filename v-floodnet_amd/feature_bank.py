@@ -26,7 +26,7 @@ DK, DV = 128, 512
 MAX_SPLIT = 20            # memory-read apply slices (o_part slabs)
 MAX_SPLIT_SCAN = 256      # bank slices (work items per query tile and object) of the persistent scan kernels
 QT, QT_SCAN, CH = 64, 128, 64
-MAX_HW = 32768           # include/vfn_hip.h VFN_BANK_MAX_HW
+MAX_HW = _lib.DEFINES['VFN_BANK_MAX_HW']
 
 
 def pick_scan_slices(hw, obj_n, b_upper, target_items=1536, min_chunks=8):

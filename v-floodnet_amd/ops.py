@@ -60,8 +60,7 @@ def conv_cfg_kind(cfg):
     return _lib.lib().vfn_conv_cfg_kind(int(cfg))
 
 
-SK_WS_FLOATS = 16 * 1024 * 1024       # include/vfn_hip.h VFN_CONV_SK_WS_FLOATS / VFN_CONV_SK_MAX_TILES
-SK_MAX_TILES = 16384
+SK_WS_FLOATS, SK_MAX_TILES = _lib.DEFINES['VFN_CONV_SK_WS_FLOATS'], _lib.DEFINES['VFN_CONV_SK_MAX_TILES']
 _sk_scratch = {}
 
 
@@ -862,7 +861,7 @@ def waterlevel_draw(overlay, boxes, log, t):
 
 
 # --------------------------------------------------------------------------- reference boxes followed through the clip
-TRACK_MAX_SIDE, TRACK_MAX_RADIUS = 512, 32          # include/vfn_hip.h
+TRACK_MAX_SIDE, TRACK_MAX_RADIUS = _lib.DEFINES['VFN_TRACK_MAX_SIDE'], _lib.DEFINES['VFN_TRACK_MAX_RADIUS']
 
 
 def track_luma(frame, out=None):
