@@ -82,10 +82,14 @@ __global__ void resize_nearest_kernel(const float* __restrict__ in, float* __res
 
 __global__ void softmax_objects_kernel(const float* __restrict__ score, float* __restrict__ prob, int obj_n, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        float v[MAX_OBJ], m = -INFINITY, s = 0.f;
+        float v[MAX_OBJ], m = -INFINITY;
         for (int o = 0; o < obj_n; ++o) { v[o] = score[(size_t)o * n + i]; m = fmaxf(m, v[o]); }
-        for (int o = 0; o < obj_n; ++o) { v[o] = expf(v[o] - m); s += v[o]; }
-        for (int o = 0; o < obj_n; ++o) prob[(size_t)o * n + i] = v[o] / s;
+        // the normaliser is summed in double and rounded once: a float running sum of 8 terms left the column sums up to
+        // 2.8e-07 from 1 (tests/test_forward_kernels_gpu.py); now every probability carries its own rounding only
+        double s = 0.0;
+        for (int o = 0; o < obj_n; ++o) { v[o] = expf(v[o] - m); s += (double)v[o]; }
+        const float sf = (float)s;
+        for (int o = 0; o < obj_n; ++o) prob[(size_t)o * n + i] = v[o] / sf;
     }
 }
 
