@@ -319,7 +319,9 @@ int vfn_stem_wgrad_f32(const float* x, const float* g, const float* rowscale, fl
  *           F(4x4, 3x3) filter banks, xi = 6 i + j, computed in float64; cout_ld = rows per bank, kh = kw = 3)
  *   kind 5  dst[((xi * cout_ld + dst_row0 + ci) * dst_ld + dst_col0 + co]          = (G g' G^T)[xi], g' = src[co][ci] flipped  (the
  *           banks of the data-gradient convolution; cout_ld = rows per bank)
- *           -- kinds 4 / 5 take ceil(cout * cin / vfn_refresh_elems_per_block()) workgroups --
+ *   kind 6  dst[((xi * cout_ld + dst_row0 + co) * dst_ld + ci]                     = (G g G^T)[xi], g = src[co][ci]   (Winograd
+ *           F(6x6, 3x3) filter banks of vfn_winograd6.h, xi = 8 i + j, 64 banks; float64 with every operation rounded on its own)
+ *           -- kinds 4 / 5 / 6 take ceil(cout * cin / vfn_refresh_elems_per_block()) workgroups --
  *   gamma / var / eps (optional): the value is multiplied by gamma[co] / sqrt(var[co] + eps) (a frozen BatchNorm's scale).
  *   block0: first workgroup of the entry; an entry takes ceil(cout * cin * kh * kw / vfn_refresh_elems_per_block()) workgroups and
  *   the table is ordered by block0. */

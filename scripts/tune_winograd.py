@@ -1,8 +1,11 @@
 """Per layer shape: the direct implicit-GEMM convolution (tuned choice) against Winograd F(4x4, 3x3) (input transform + the 36
-batched-filter GEMMs with their best tile configuration + output transform), every 3x3 / stride-1 layer of the C2 / C3 / C5 plans.
+batched-filter GEMMs with their best tile configuration + output transform), every 3x3 / stride-1 layer of the C2 / C3 / C5 plans;
+then (fp32, VFN_WINO_F6=1, the default) every shape that runs as Winograd again as F(6x6, 3x3): its 64 GEMMs with the best persistent
+configuration, the three launches of either form timed with a residual (F(6x6)'s slower output kernel).
 usage: tune_winograd.py [HxW ...] (default: the bench sizes; 400x400 = the training sample).  VFN_WINO_GROUP=n: also the shapes of groups of n frames.
-Writes gpurun_out/wino_gfx950.json ("M,cin,cout" -> 1 where Winograd is at least 5 % faster) and the GEMM shapes' entries
-into gpurun_out/tuned_gfx950.json."""
+Writes, into the directory $VFN_TUNE_OUT (default tune_out/): wino_gfx950.json ("M,cin,cout" -> 1 where Winograd is at least 5 % faster than direct, 2 where F(6x6) is at least
+3 % faster than F(4x4) on top of that), the GEMM shapes' entries into tuned_gfx950.json (F(6x6): tuned_gfx950_wino6.json) and the per-layer figures into
+tune_winograd_report*.json / tune_winograd6_report.json."""
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['VFN_WINOGRAD'] = '0'
@@ -34,6 +37,36 @@ def time_list(lst, iters=10):
 RETUNE = os.environ.get('VFN_WINO_RETUNE', '0') == '1'    # measure the shapes of the shipped table again (new kernels)
 SHIPPED = engine._WINO_TABLE if MODE == 0 else engine._WINO_TABLE_BF16
 table, report = ({} if RETUNE else dict(SHIPPED)), []          # (otherwise shapes measured before stay as they are)
+F6 = MODE == 0 and os.environ.get('VFN_WINO_F6', '1') == '1'
+report6, seen6 = [], set()
+
+
+def measure_f6(p, l, d, layer, key):
+    """F(4x4) (the table's GEMM choice) against F(6x6) (its best persistent configuration) on the layer's tensors, both with a residual."""
+    x = torch.randn(d.N, d.H, d.W, d.Cin, device=dev)
+    out = torch.empty(d.N, d.H, d.W, d.Cout, device=dev)
+    res = torch.randn(d.N, d.H, d.W, d.Cout, device=dev)
+    p._ws_cur, p._cnt_cur = p.ws, p.cnt
+    rec = dict(layer=l.name, key=key)
+    for tile in (4, 6):
+        seq = []
+        p._conv_winograd(seq, layer, x, out, d.N, d.H, d.W, res, bool(d.relu_in), bool(d.relu_out), 'probe', None, 0, 0, tile)
+        dg = seq[1].args[0]
+        if tile == 6:
+            best, t_best = None, None
+            for c in ops.wino_gemm_cfg_options(dg.w_batch_rows, dg.Cout):
+                engine.apply_choice(dg, (c, 1, 0), p.ws, p.cnt)
+                t = time_list([engine.Launch(ops.conv2d_launch, (dg, c, 0), 'g')], iters=5)
+                if t_best is None or t < t_best:
+                    best, t_best = (c, 1, 0), t
+            engine.apply_choice(dg, best, p.ws, p.cnt)
+            seq[1].args = (dg, best[0], 0)
+            engine._TUNED_WINO6[(dg.M, dg.Cout, dg.Cin)] = best
+        rec['f%d' % tile] = dict(rows=dg.w_batch_rows, gemm=[dg.M, dg.Cout, dg.Cin], cfg=ops.conv_cfg_name(seq[1].args[1]), wgs=((seq[1].args[1] - ops.WINO_GEMM_CFG0) >> 3) * 128 if seq[1].args[1] >= ops.WINO_GEMM_CFG0 else 0,
+                                 us=round(time_list(seq), 1), input_us=round(time_list([seq[0]]), 1), gemm_us=round(time_list([seq[1]]), 1),
+                                 output_us=round(time_list([seq[2]]), 1))
+    rec['use_f6'] = int(rec['f6']['us'] < 0.97 * rec['f4']['us'])
+    return rec
 sizes = [tuple(int(v) for v in a.split('x')) for a in sys.argv[1:]] or [(480, 854), (480, 853), (480, 800)]
 layers = []          # every ConvLayer of the engine, by identity of its packed filters
 def walk(o):
@@ -63,6 +96,11 @@ for (h, w) in sizes:
                 continue
             key = (d.M, d.Cin, d.Cout)
             if key in table:
+                if F6 and table[key] >= 1 and key not in seen6 and (RETUNE or table[key] == 1 or os.environ.get('VFN_WINO_F6_AGAIN') == '1'):
+                    seen6.add(key)
+                    report6.append(measure_f6(p, l, d, layer, key))
+                    table[key] = 2 if report6[-1]['use_f6'] else 1
+                    print(report6[-1], flush=True)
                 continue
             t_dir = time_list([l])
             # the Winograd sequence for the same tensors
@@ -108,10 +146,19 @@ for (h, w) in sizes:
             report.append(dict(layer=l.name, key=key, direct_us=round(t_dir, 1), wino_us=round(t_w, 1), input_us=round(t_in, 1), gemm_us=round(t_best, 1),
                                output_us=round(t_out, 1), gemm_cfg=list(best), use=table[key]))
             print(report[-1], flush=True)
+            if F6 and table[key]:
+                seen6.add(key)
+                report6.append(measure_f6(p, l, d, layer, key))
+                table[key] = 2 if report6[-1]['use_f6'] else 1
+                print(report6[-1], flush=True)
 for k_, v_ in SHIPPED.items():
     table.setdefault(k_, v_)                           # (shapes of other frame sizes keep their entries)
-os.makedirs('gpurun_out', exist_ok=True)
-json.dump({','.join(str(x) for x in k): v for k, v in sorted(table.items())}, open('gpurun_out/wino_gfx950%s.json' % ('' if MODE == 0 else '_bf16'), 'w'), indent=0)
-json.dump(report, open('gpurun_out/r05_tune_winograd_report%s.json' % ('' if MODE == 0 else '_bf16'), 'w'), indent=1)
-engine.save_tuned('gpurun_out/' + os.path.basename(engine._TABLE_PATHS[MODE]), MODE)
-print(sum(table.values()), 'of', len(table), 'shapes use Winograd')
+OUT = os.environ.get('VFN_TUNE_OUT', 'tune_out')
+os.makedirs(OUT, exist_ok=True)
+json.dump({','.join(str(x) for x in k): v for k, v in sorted(table.items())}, open(OUT + '/wino_gfx950%s.json' % ('' if MODE == 0 else '_bf16'), 'w'), indent=0)
+json.dump(report, open(OUT + '/tune_winograd_report%s.json' % ('' if MODE == 0 else '_bf16'), 'w'), indent=1)
+if F6:
+    json.dump(report6, open(OUT + '/tune_winograd6_report.json', 'w'), indent=1)
+    engine.save_tuned(OUT + '/' + os.path.basename(engine._TUNED_WINO6_PATH), 'wino6')
+engine.save_tuned(OUT + '/' + os.path.basename(engine._TABLE_PATHS[MODE]), MODE)
+print(sum(1 for v in table.values() if v), 'of', len(table), 'shapes use Winograd,', sum(1 for v in table.values() if v == 2), 'of them F(6x6)')

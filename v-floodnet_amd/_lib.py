@@ -131,6 +131,9 @@ def parse_header(text):
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_hip.h')) as _f:
     DEFINES, ENUMS, STRUCTS, SIGNATURES = parse_header(_f.read())     # SIGNATURES: name -> argtypes (restype is int everywhere)
 ALL_SYMBOLS = sorted(SIGNATURES)
+# the second part of the ABI (entry points only, no structs): Winograd F(6x6, 3x3), include/vfn_winograd6.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_winograd6.h')) as _f:
+    SIGNATURES_WINOGRAD6 = parse_header(_f.read())[3]
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
     DEFINES['VFN_TRAIN_AUG_MAX_' + _k] for _k in ('T', 'SIDE', 'OUT', 'OBJ'))
@@ -165,11 +168,11 @@ def lib():
                 '(python -c "import __graft_entry__ as g; g.build()" or make -C v-floodnet_amd/csrc)')
         L = C.CDLL(LIB_PATH)
 
-        def declare(name):
+        def declare(name, signatures=SIGNATURES, header='vfn_hip.h'):
             if not hasattr(L, name):
-                raise RuntimeError(f'{LIB_PATH} lacks {name}, which include/vfn_hip.h declares: rebuild it (make -C v-floodnet_amd/csrc)')
+                raise RuntimeError(f'{LIB_PATH} lacks {name}, which include/{header} declares: rebuild it (make -C v-floodnet_amd/csrc)')
             fn = getattr(L, name)
-            fn.argtypes, fn.restype = SIGNATURES[name], C.c_int
+            fn.argtypes, fn.restype = signatures[name], C.c_int
             return fn
 
         if declare('vfn_abi_version')() != ABI_VERSION:
@@ -182,6 +185,8 @@ def lib():
                                    f'{C.sizeof(cls)} in this binding: rebuild it (make -C v-floodnet_amd/csrc)')
         for name in SIGNATURES:
             declare(name)
+        for name in SIGNATURES_WINOGRAD6:
+            declare(name, SIGNATURES_WINOGRAD6, 'vfn_winograd6.h')
         _lib = L
     return _lib
 

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "conv_internal.h"
 #include "../../include/vfn_hip.h"
+#include "../../include/vfn_winograd6.h"
 
 namespace {
 
@@ -184,6 +185,179 @@ void winograd_output_kernel(const float* __restrict__ Mb, int rows_pad, int N, i
                 const int row = rowi[a][b];
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), ro,
                                                        row >= 0 ? (row * out_ld + c4 * 4) * 4 : 0x7ffffff0, 0, 0);
+            }
+        }
+    }
+}
+
+// ---- Winograd F(6x6, 3x3) for the f32 inference layers: 64 transform-domain values per 36 outputs (1.78 per output) instead of
+// F(4x4)'s 36 per 16 (2.25): 21 % fewer rows of V and M, GEMM FLOP and transform bytes before tile rounding.  Points 0, +-1, +-2,
+// +-1/2, inf; about twice F(4x4)'s rounding (tests/test_winograd6_gpu.py).  Same load / store form as the kernels above; a thread
+// owns TWO channels of a tile (its 8x8 patch is 128 registers), so a wave's loads and stores are contiguous 512-byte rows.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// t = B^T v (8 values)
+__device__ __forceinline__ void bt8(const f32x2 (&v)[8], f32x2 (&t)[8]) {
+    const f32x2 e1 = v[2] + v[6] - 4.25f * v[4], o1 = v[1] + v[5] - 4.25f * v[3];
+    const f32x2 e2 = v[6] + 0.25f * v[2] - 1.25f * v[4], o2 = 0.5f * v[1] - 2.5f * v[3] + 2.f * v[5];
+    const f32x2 e3 = v[6] + 4.f * v[2] - 5.f * v[4], o3 = 2.f * v[1] - 2.5f * v[3] + 0.5f * v[5];
+    t[0] = v[0] - v[6] + 5.25f * (v[4] - v[2]);
+    t[1] = e1 + o1;
+    t[2] = e1 - o1;
+    t[3] = e2 + o2;
+    t[4] = e2 - o2;
+    t[5] = e3 + o3;
+    t[6] = e3 - o3;
+    t[7] = v[7] - v[1] + 5.25f * (v[3] - v[5]);
+}
+
+inline int winograd6_tiles(int N, int H, int W) { return N * ((H + 5) / 6) * ((W + 5) / 6); }
+
+// V [64][rows_pad][C]: rows >= the tile count are written as zeros (the scratch is shared between layers of different shapes).
+// Addresses: one VGPR per tensor -- the tap (a, b) of the patch and the component xi are wave-uniform displacements ((a W + b) pixels,
+// xi rows_pad C floats), so they ride in the scalar offset of the buffer instructions instead of 64 address registers.
+__global__ __launch_bounds__(256, 2)
+void winograd6_input_kernel(const float* __restrict__ x, int N, int H, int W, int C, int ld_x, int relu, float* __restrict__ V,
+                            int rows_pad) {
+    const int th = (H + 5) / 6, tw = (W + 5) / 6, tiles = N * th * tw;
+    const int c2n = C / 2;
+    const long long total = (long long)rows_pad * c2n;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)((size_t)N * H * W * ld_x * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(V, 0, (int)((size_t)64 * rows_pad * C * 4), 0x00020000);
+    const int comp4 = rows_pad * C * 4;                       // bytes per component
+    const float floor_ = relu ? 0.f : -INFINITY;
+    // (one pass: 64 rows_pad C floats stay below 2 GiB, so the grid always covers every thread's work item -- and a loop would make
+    // the compiler keep all the scalar displacements below alive at once)
+    const long long i = vfn_xcd_block(blockIdx.x, gridDim.x) * (long long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    {
+        const int c2 = (int)(i % c2n);
+        const int tile = (int)(i / c2n);
+        const int vo = (tile * C + c2 * 2) * 4;
+        if (tile >= tiles) {
+#pragma unroll
+            for (int xi = 0; xi < 64; ++xi) __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, rv, vo, xi * comp4, 0);
+            return;
+        }
+        const int tx = tile % tw, ty = (tile / tw) % th, n = tile / (tw * th);
+        const int y0 = 6 * ty - 1, x0 = 6 * tx - 1;
+        const int base = (((n * H + y0) * W + x0) * ld_x + c2 * 2) * 4;      // (the patch's first tap; outside the image for edge tiles)
+        f32x2 d[8][8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool ok = (unsigned)(y0 + a) < (unsigned)H && (unsigned)(x0 + b) < (unsigned)W;
+                d[a][b] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, ok ? base + (a * W + b) * ld_x * 4 : 0x7ffffff0, 0, 0));
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) d[a][b][e] = vfn_floor_nan(d[a][b][e], floor_);
+        // columns: d <- B^T d, then rows: V = d B
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            f32x2 v[8], t[8];
+#pragma unroll
+            for (int a = 0; a < 8; ++a) v[a] = d[a][b];
+            bt8(v, t);
+#pragma unroll
+            for (int a = 0; a < 8; ++a) d[a][b] = t[a];
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            f32x2 t[8];
+            bt8(d[a], t);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, t[b]), rv, vo, (a * 8 + b) * comp4, 0);
+        }
+    }
+}
+
+// y = A^T m (8 values -> 6)
+__device__ __forceinline__ void at8(const f32x2 (&m)[8], f32x2 (&y)[6]) {
+    const f32x2 s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4], s56 = m[5] + m[6], d56 = m[5] - m[6];
+    y[0] = m[0] + s12 + s34 + s56;
+    y[1] = d12 + 2.f * d34 + 0.5f * d56;
+    y[2] = s12 + 4.f * s34 + 0.25f * s56;
+    y[3] = d12 + 8.f * d34 + 0.125f * d56;
+    y[4] = s12 + 16.f * s34 + 0.0625f * s56;
+    y[5] = d12 + 32.f * d34 + 0.03125f * d56 + m[7];
+}
+
+// the 64 components are loaded back to back (one address register: the component rides in the scalar offset), the residual taps of
+// the 36 output pixels are raw buffer loads issued together behind the first transform stage, the stores are buffer stores whose
+// offset is out of range for pixels past the image edge
+// RES: with a residual (its 36 taps are 72 more registers: one workgroup per CU instead of two)
+template <bool RES>
+__global__ __launch_bounds__(256, RES ? 1 : 2)
+void winograd6_output_kernel(const float* __restrict__ Mb, int rows_pad, int N, int H, int W, int Cout,
+                             const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ res, int res_ld,
+                             int res_mod, int relu_out, float* __restrict__ out, int out_ld) {
+    const int th = (H + 5) / 6, tw = (W + 5) / 6;
+    const int c2n = Cout / 2;
+    const long long total = (long long)N * th * tw * c2n;
+    const int npix = N * H * W;
+    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Mb), 0, (int)((size_t)64 * rows_pad * Cout * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)npix * out_ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(res ? res : Mb), 0,
+                                                                        res ? (int)((size_t)(res_mod > 0 ? res_mod : npix) * res_ld * 4) : 0, 0x00020000);
+    const float floor_ = relu_out ? 0.f : -INFINITY;
+    const int comp4 = rows_pad * Cout * 4;
+    // (one pass: 64 rows_pad C floats stay below 2 GiB, so the grid always covers every thread's work item -- and a loop would make
+    // the compiler keep all the scalar displacements below alive at once)
+    const long long i = vfn_xcd_block(blockIdx.x, gridDim.x) * (long long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    {
+        int iw = (int)i;
+        const int mo = ((iw / c2n) * Cout + (iw % c2n) * 2) * 4;
+        f32x2 m[8][8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) m[a][b] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rm, mo, (a * 8 + b) * comp4, 0));
+        f32x2 t[8][6];                            // t = M A  (rows of M through A^T)
+#pragma unroll
+        for (int a = 0; a < 8; ++a) at8(m[a], t[a]);
+        __builtin_amdgcn_sched_barrier(0);        // (the 36 residual taps go out once M's 128 registers are free, not beside them)
+        asm volatile("" : "+v"(iw));              // (... and the tile's coordinates are worked out here, not kept alive beside M)
+        const int c2 = iw % c2n, tile = iw / c2n;
+        const int tx = tile % tw, ty = (tile / tw) % th, n = tile / (tw * th);
+        f32x2 sc = {1.f, 1.f}, sh = {0.f, 0.f};
+        if (scale) sc = *reinterpret_cast<const f32x2*>(scale + c2 * 2);
+        if (shift) sh = *reinterpret_cast<const f32x2*>(shift + c2 * 2);
+        // the 36 pixels of the tile: row0 + a W + b, invalid past the image edge
+        const int y0 = 6 * ty, x0 = 6 * tx, row0 = (n * H + y0) * W + x0;
+        // (res_mod: the residual repeats every res_mod pixels, a whole number of images -- a tile never wraps)
+        const int rb = ((row0 - (res_mod > 0 ? (n * H * W) / res_mod * res_mod : 0)) * res_ld + c2 * 2) * 4;
+        f32x2 rv[RES ? 6 : 1][RES ? 6 : 1];
+        if constexpr (RES) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b < 6; ++b) {
+                    const bool ok = y0 + a < H && x0 + b < W;
+                    rv[a][b] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, ok ? rb + (a * W + b) * res_ld * 4 : 0x7ffffff0, 0, 0));
+                }
+        }
+        const int oo = (row0 * out_ld + c2 * 2) * 4;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            f32x2 col[8], y[6];
+#pragma unroll
+            for (int a = 0; a < 8; ++a) col[a] = t[a][b];
+            at8(col, y);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                f32x2 v;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) v[e] = vfn_floor_nan(y[a][e] * sc[e] + sh[e] + (RES ? rv[a][b][e] : 0.f), floor_);
+                const bool ok = y0 + a < H && x0 + b < W;
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), ro, ok ? oo + (a * W + b) * out_ld * 4 : 0x7ffffff0, 0, 0);
             }
         }
     }
@@ -599,6 +773,31 @@ extern "C" int vfn_winograd_output_f32(const float* Mb, int rows_pad, int N, int
     if (!tensors_fit_32bit(N, H, W, out_ld, res ? res_ld : 0, 0, res_mod)) return VFN_ERR_ARG;
     hipLaunchKernelGGL(winograd_output_kernel<false>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift,
                        res, res_ld, res_mod, relu_out, out, out_ld, (const float*)nullptr, 0, 0);
+    return vfn_check_launch();
+}
+
+// F(6x6, 3x3) (include/vfn_winograd6.h): V [64][rows_pad][C] of the 8x8 patches at stride 6, rows past the tiles zeroed; the GEMMs are
+// vfn_winograd_gemm_f32 with comps = 64; the output transform carries the epilogue of vfn_winograd_output_f32
+extern "C" int vfn_winograd6_input_f32(const float* x, int N, int H, int W, int C, int ld_x, int relu, float* V, int rows_pad, void* stream) {
+    if (!x || !V || N < 1 || H < 1 || W < 1 || C < 4 || C % 4 || ld_x < C || ld_x % 4 || rows_pad < winograd6_tiles(N, H, W)) return VFN_ERR_ARG;
+    if (!tensors_fit_32bit(N, H, W, ld_x, 0, 0, 0) || (long long)64 * rows_pad * C * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
+    hipLaunchKernelGGL(winograd6_input_kernel, dim3(((long long)rows_pad * (C / 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, N, H, W, C, ld_x, relu,
+                       V, rows_pad);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_winograd6_output_f32(const float* Mb, int rows_pad, int N, int H, int W, int Cout, const float* scale, const float* shift,
+                                        const float* res, int res_ld, int res_mod, int relu_out, float* out, int out_ld, void* stream) {
+    if (!Mb || !out || N < 1 || H < 1 || W < 1 || Cout < 4 || Cout % 4 || out_ld < Cout || out_ld % 4 || (res && res_ld % 4) ||
+        rows_pad < winograd6_tiles(N, H, W) || res_mod < 0 || (res && res_mod % (H * W))) return VFN_ERR_ARG;
+    if (!tensors_fit_32bit(N, H, W, out_ld, res ? res_ld : 0, 0, res_mod) || (long long)64 * rows_pad * Cout * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
+    const dim3 grid(((long long)winograd6_tiles(N, H, W) * (Cout / 2) + 255) / 256);
+    if (res)
+        hipLaunchKernelGGL(winograd6_output_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift, res, res_ld,
+                           res_mod, relu_out, out, out_ld);
+    else
+        hipLaunchKernelGGL(winograd6_output_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift, res, res_ld,
+                           res_mod, relu_out, out, out_ld);
     return vfn_check_launch();
 }
 

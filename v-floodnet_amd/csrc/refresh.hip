@@ -19,6 +19,44 @@ __device__ __forceinline__ float bn_scale(const float* gamma, const float* var, 
     return __fdiv_rn(gamma[c], __fsqrt_rn(__fadd_rn(var[c], eps)));
 }
 
+// kind 6: the 64 filter banks U = G g G^T of Winograd F(6x6, 3x3) (points 0, +-1, +-2, +-1/2, inf), one (filter, channel) pair per
+// thread, forward layout.  Every product and sum is rounded on its own, in the order ops.pack_winograd6_weight uses on the host:
+// the two images agree bit for bit.
+__device__ void winograd6_banks(const vfn_refresh_filter& e, long long base) {
+#pragma clang fp contract(off)
+    const long long pairs = (long long)e.cout * e.cin;
+    const double G[8][3] = {{1.0, 0.0, 0.0}, {-2.0 / 9, -2.0 / 9, -2.0 / 9}, {-2.0 / 9, 2.0 / 9, -2.0 / 9},
+                            {1.0 / 90, 1.0 / 45, 2.0 / 45}, {1.0 / 90, -1.0 / 45, 2.0 / 45},
+                            {32.0 / 45, 16.0 / 45, 8.0 / 45}, {32.0 / 45, -16.0 / 45, 8.0 / 45}, {0.0, 0.0, 1.0}};
+    for (int i = threadIdx.x; i < ELEMS_PER_BLOCK; i += 256) {
+        const long long idx = base + i;
+        if (idx >= pairs) return;
+        const int ci = (int)(idx % e.cin), co = (int)(idx / e.cin);
+        const float* g = e.src + ((size_t)co * e.cin_total + e.cin_off + ci) * 9;
+        const float sc = e.gamma ? bn_scale(e.gamma, e.var, e.eps, co) : 1.f;
+        double w[3][3];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            float v = g[t];
+            if (e.gamma) v = __fmul_rn(v, sc);
+            w[t / 3][t % 3] = (double)v;
+        }
+        double tmp[8][3];
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) tmp[a][b] = (G[a][0] * w[0][b] + G[a][1] * w[1][b]) + G[a][2] * w[2][b];
+        float* dst = e.dst + (size_t)(e.dst_row0 + co) * e.dst_ld + ci;
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const double u = (tmp[a][0] * G[b][0] + tmp[a][1] * G[b][1]) + tmp[a][2] * G[b][2];
+                dst[(size_t)(a * 8 + b) * e.cout_ld * e.dst_ld] = (float)u;
+            }
+    }
+}
+
 __global__ __launch_bounds__(256)
 void refresh_filters_kernel(const vfn_refresh_filter* __restrict__ table, int n) {
     // the entry this block works on: the last one whose first block is <= blockIdx.x
@@ -30,6 +68,10 @@ void refresh_filters_kernel(const vfn_refresh_filter* __restrict__ table, int n)
     const vfn_refresh_filter e = table[lo];
     const int T = e.kh * e.kw;
     const long long base = (long long)((int)blockIdx.x - e.block0) * ELEMS_PER_BLOCK;
+    if (e.kind == 6) {
+        winograd6_banks(e, base);
+        return;
+    }
     if (e.kind >= 4) {                           // Winograd F(4x4, 3x3) filter banks U = G g G^T, one (filter, channel) pair per thread
         const long long pairs = (long long)e.cout * e.cin;
         const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},

@@ -38,6 +38,19 @@ _TUNED_BF16X3 = {}   # ... and for the bf16x3 kernel
 _TUNED_BF16X3_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_bf16x3.json')
 _TABLES = (_TUNED, _TUNED_BF16, _TUNED_BF16X3)                 # by ops.MODES value
 _TABLE_PATHS = (_TUNED_PATH, _TUNED_BF16_PATH, _TUNED_BF16X3_PATH)
+# the transform-domain GEMMs of Winograd F(6x6, 3x3) (f32): (64 * rows, Cout, Cin) -> persistent configuration.  Their own table and
+# file: the row counts are multiples of 64, not of 36 x 256, and a shape may coincide with an F(4x4) one whose tile does not divide the rows
+_TUNED_WINO6 = {}
+_TUNED_WINO6_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_wino6.json')
+
+
+def is_wino6_desc(d):
+    return d.w_batch_rows > 0 and d.M == 64 * d.w_batch_rows
+
+
+def table_of(d, mode):
+    """The measured table a descriptor's tile choice is looked up in."""
+    return _TUNED_WINO6 if mode == 0 and is_wino6_desc(d) else _TABLES[mode]
 
 
 def _load_tuned():
@@ -45,7 +58,7 @@ def _load_tuned():
     import os
     if os.environ.get('VFN_IGNORE_TUNED') == '1':
         return
-    for path, table in zip(_TABLE_PATHS, _TABLES):
+    for path, table in zip(_TABLE_PATHS + (_TUNED_WINO6_PATH,), _TABLES + (_TUNED_WINO6,)):
         alt = os.environ.get('VFN_TUNED_DIR')                     # (A/B of two sets of tables: same file names in another directory)
         if alt and os.path.isfile(os.path.join(alt, os.path.basename(path))):
             path = os.path.join(alt, os.path.basename(path))
@@ -59,9 +72,10 @@ def _load_tuned():
 
 
 def save_tuned(path=None, mode=0):
+    """``mode`` = 'wino6': the F(6x6, 3x3) GEMMs' table."""
     import json
-    table = _TABLES[mode]
-    with open(path or _TABLE_PATHS[mode], 'w') as f:
+    table = _TUNED_WINO6 if mode == 'wino6' else _TABLES[mode]
+    with open(path or (_TUNED_WINO6_PATH if mode == 'wino6' else _TABLE_PATHS[mode]), 'w') as f:
         json.dump({','.join(str(x) for x in k): list(v) for k, v in sorted(table.items())}, f, indent=0)
 
 
@@ -88,6 +102,11 @@ _TRAIN_SLOTS = int(os.environ.get('VFN_TRAIN_SLOTS', 2))      # training plans s
 # (wino_gfx950.json: "M,cin,cout" -> 0 / 1, scripts/tune_winograd.py; shapes it lacks: >= 128 channels either side and at least
 # VFN_WINOGRAD_MIN_M output pixels), 2 = every eligible layer, 0 = off (the direct implicit GEMM everywhere)
 _WINOGRAD = os.environ.get('VFN_WINOGRAD', '1')
+# F(6x6, 3x3) instead of F(4x4, 3x3) for the f32 inference plans' Winograd layers (64 components of 6x6 tiles: 1.78 transform-domain
+# values per output instead of 2.25): 1 (default) = where the table holds 2 for the shape (the layer's three launches measured
+# faster than F(4x4)'s, scripts/tune_winograd.py), 0 = F(4x4) everywhere (A/B runs in one tree), 2 = every Winograd layer that
+# may (tests).  The bf16 modes, training plans and VFN_WINOGRAD=2 keep F(4x4).
+_WINOGRAD_F6 = os.environ.get('VFN_WINOGRAD_F6', '1')
 _WINOGRAD_LP = os.environ.get('VFN_WINOGRAD_LP', '1') == '1'        # Winograd layers in the plain-bf16 mode too (bf16 V / U, vfn_winograd_gemm_bf16)
 _WINOGRAD_MIN_M = int(os.environ.get('VFN_WINOGRAD_MIN_M', 10000))
 _WINO_TABLE = {}
@@ -252,7 +271,7 @@ def tune_desc(d, bf, ws, cnt, iters=3, cfg_filter=None, allow_split=True):
             continue
         if cfg_filter is not None and not cfg_filter(key, c):
             continue
-        if d.cout_pad < ((d.Cout + bn - 1) // bn) * bn:
+        if d.cout_pad < ((d.Cout + bn - 1) // bn) * bn or (d.w_batch_rows > 0 and d.w_batch_rows % bm):
             continue
         if (bn > 64 and d.Cout <= 32) or (bn > 128 and d.Cout < 256):
             continue
@@ -322,6 +341,11 @@ class ConvLayer:
                     continue
                 w = self.w[:self.cout].view(self.cout, 3, 3, self.cin).permute(0, 3, 1, 2)
                 t.copy_(ops.pack_winograd_weight(w).to(t.device))
+            elif mode == 'wino6':
+                if self._wino_src is not None:
+                    continue
+                w = self.w[:self.cout].view(self.cout, 3, 3, self.cin).permute(0, 3, 1, 2)
+                t.copy_(ops.pack_winograd6_weight(w).to(t.device))
             elif mode == 'wino_bf16':
                 w = self.w[:self.cout].view(self.cout, 3, 3, self.cin).permute(0, 3, 1, 2)
                 t.copy_(ops.pack_winograd_weight_bf16(w).to(t.device))
@@ -347,6 +371,19 @@ class ConvLayer:
                     reg.add_filter(weight, self._w_lp['wino'], WINO, cin=self.cin, cin_off=cin_off, dst_ld=self.cin, dst_row0=row0,
                                    cout_ld=self._w_lp['wino'].shape[0] // 36)
         return self._w_lp['wino']
+
+    def w_wino6(self):
+        """The 64 filter banks of Winograd F(6x6, 3x3) (ops.pack_winograd6_weight; refresh kind WINO6), built once."""
+        if 'wino6' not in self._w_lp:
+            assert self.k == 3
+            w = self.w[:self.cout].view(self.cout, 3, 3, self.cin).permute(0, 3, 1, 2)
+            self._w_lp['wino6'] = ops.pack_winograd6_weight(w).to(self.w.device)
+            if self._wino_src is not None:
+                from .refresh import WINO6
+                for reg, weight, cin_off, row0 in self._wino_src:
+                    reg.add_filter(weight, self._w_lp['wino6'], WINO6, cin=self.cin, cin_off=cin_off, dst_ld=self.cin, dst_row0=row0,
+                                   cout_ld=self._w_lp['wino6'].shape[0] // 64)
+        return self._w_lp['wino6']
 
     def w_wino_bf16(self):
         """... rounded once to bf16: the filter operand of the plain-bf16 mode's Winograd layers (vfn_winograd_gemm_bf16)."""
@@ -624,7 +661,9 @@ class FramePlan:
             f32_out = True                                    # (a consumer in another mode reads the f32 tensor)
         if ((bf == 0 or (bf == 1 and _WINOGRAD_LP and not self.keep_acts and layer.cin % 64 == 0)) and in_ld is None and
                 (_WINOGRAD_TRAIN or not self.keep_acts) and x.shape[-1] == layer.cin and self.eng.use_winograd(layer, N * H * Wd, bf)):
-            return self._conv_winograd(lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf)
+            tile = 6 if (bf == 0 and not self.keep_acts and res_mod % (H * Wd) == 0 and      # (a residual that repeats per image or not at all)
+                         self.eng.winograd_tile(layer, N * H * Wd) == 6) else 4
+            return self._conv_winograd(lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf, tile)
         d = ops.make_conv_desc(x, layer.w, layer.cout, layer.k, layer.k, layer.stride, layer.pad, out,
                                layer.scale, layer.shift, res, relu_in, relu_out,
                                cin=layer.cin, in_ld=in_ld if in_ld is not None else x.shape[-1],
@@ -651,35 +690,42 @@ class FramePlan:
         lst.append(Launch(ops.conv2d_launch, (d, cfg, bf), f'{name}[{d.M}x{layer.cout}x{K}]', 2.0 * d.M * layer.cout * K))
         return out
 
-    def _conv_winograd(self, lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf=0):
+    def _conv_winograd(self, lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf=0, tile=4):
         """A 3x3 / stride-1 layer as Winograd F(4x4, 3x3): input transform, the 36 transform-domain GEMMs as ONE batched-filter
         launch of the convolution kernels (tile choice from the same tables / tuner, keyed by the GEMM's shape), output transform
-        with the layer's epilogue (csrc/conv_winograd.hip)."""
-        rows = ops.winograd_rows(N, H, Wd)
+        with the layer's epilogue (csrc/conv_winograd.hip).  ``tile`` = 6 (f32): F(6x6, 3x3), 64 GEMMs over fewer, larger tiles."""
+        comps = 64 if tile == 6 else 36
+        rows = ops.winograd6_rows(N, H, Wd) if tile == 6 else ops.winograd_rows(N, H, Wd)
         key = id(self._ws_cur)
-        need_v, need_m = 36 * rows * layer.cin, 36 * rows * layer.cout
+        need_v, need_m = comps * rows * layer.cin, comps * rows * layer.cout
         V, Mb = self._wino.get(key, (None, None))
         if V is None or V.numel() < need_v or Mb.numel() < need_m:
             dev = self.eng.device
             V = torch.zeros(max(need_v, V.numel() if V is not None else 0), device=dev)
             Mb = torch.empty(max(need_m, Mb.numel() if Mb is not None else 0), device=dev)
             self._wino[key] = (V, Mb)                      # (launches built earlier keep their own, smaller buffers alive)
-        Mb = Mb[:need_m].view(36 * rows, layer.cout)
+        Mb = Mb[:need_m].view(comps * rows, layer.cout)
         if bf == 1:
             # the plain-bf16 mode (round 5): V is written as bf16 by the input transform (f32 arithmetic, one rounding -- what the bf16
             # convolution does to its operands as it stages them), the filter banks are bf16, the persistent GEMM accumulates in f32
             V = V.view(torch.bfloat16)[:need_v].view(36 * rows, layer.cin)
             U = layer.w_wino_bf16()
         else:
-            V = V[:need_v].view(36 * rows, layer.cin)
-            U = layer.w_wino()
-        lst.append(Launch(ops.winograd_input, (x, V, rows, relu_in, N, H, Wd, layer.cin, x.shape[-1]), name + '.wino_in'))
-        dg = ops.make_winograd_gemm_desc(V, U, Mb, rows, layer.cin, layer.cout)
+            V = V[:need_v].view(comps * rows, layer.cin)
+            U = layer.w_wino6() if tile == 6 else layer.w_wino()
+        lst.append(Launch(ops.winograd_input, (x, V, rows, relu_in, N, H, Wd, layer.cin, x.shape[-1], tile), name + '.wino_in'))
+        dg = ops.make_winograd_gemm_desc(V, U, Mb, rows, layer.cin, layer.cout, comps)
         if bf:
             choice = _TABLES[bf].get((dg.M, layer.cout, layer.cin))
             if choice is None or choice[0] < ops.WINO_GEMM_CFG0:
                 tc = 5 if rows % 64 == 0 and layer.cout >= 128 and rows >= 1024 else 3
                 choice = (ops.wino_gemm_cfg(tc, 512), 1, 0)
+        elif tile == 6:
+            # rows are padded to 64 only: the persistent kernel with a tile height that divides them (the shipped table holds the
+            # measured one; otherwise 64 x 128 / 64 x 64 tiles, operands requested two K tiles ahead)
+            choice = _TUNED_WINO6.get((dg.M, layer.cout, layer.cin))
+            if choice is None or choice[0] not in ops.wino_gemm_cfg_options(rows, layer.cout):
+                choice = (ops.wino_gemm_cfg(5 if layer.cout >= 128 else 7, 768), 1, 0)
         else:
             choice = choose_cfg(dg.M, layer.cout, layer.cin, 0)
         cfg = apply_choice(dg, choice, self._ws_cur, self._cnt_cur)
@@ -687,7 +733,7 @@ class FramePlan:
         self._lp_state.pop((out.data_ptr(), tuple(out.shape)), None)
         lst.append(Launch(ops.winograd_output, (Mb, rows, out, N, H, Wd, layer.cout, layer.scale, layer.shift, res,
                                                 res.shape[-1] if res is not None else 0, res_mod, relu_out,
-                                                out_ld if out_ld is not None else out.shape[-1]), name + '.wino_out'))
+                                                out_ld if out_ld is not None else out.shape[-1], tile), name + '.wino_out'))
         return out
 
     def _trunk(self, lst, enc, bufs, N, prefix, acts=None):
@@ -1044,6 +1090,15 @@ class Engine:
         if hit is not None:
             return bool(hit)
         return layer.cin >= 128 and layer.cout >= 128 and M >= _WINOGRAD_MIN_M
+
+    def winograd_tile(self, layer, M):
+        """Output tile of an f32 inference plan's Winograd layer: 6 (F(6x6, 3x3)) where the table holds 2 for the shape, else 4.
+        See _WINOGRAD_F6 above."""
+        if _WINOGRAD_F6 == '0':
+            return 4
+        if _WINOGRAD_F6 == '2':
+            return 6
+        return 6 if _WINOGRAD != '2' and _WINO_TABLE.get((M, layer.cin, layer.cout)) == 2 else 4
 
     def layer_mode(self, name):
         for prefix, m_ in self.pmap:
@@ -1575,8 +1630,8 @@ class Engine:
                 l_side = id(lst) in side_lists
                 if l.fn is ops.conv2d_launch:
                     d = l.args[0]
-                    key = (d.M, d.Cout, d.KH * d.KW * d.Cin, int(l.args[2]))
-                    if only_missing and key[:3] in _TABLES[key[3]]:
+                    key = (d.M, d.Cout, d.KH * d.KW * d.Cin, int(l.args[2]), is_wino6_desc(d))
+                    if only_missing and key[:3] in table_of(d, key[3]):
                         continue
                     if shape_filter is not None and not shape_filter(key[:3]):      # (re-tune a subset, e.g. after a new tile shape)
                         continue
@@ -1584,8 +1639,11 @@ class Engine:
         for key, launches in seen.items():
             d = launches[0][0].args[0]
             bf = key[3]
-            best = tune_desc(d, bf, p.ws, p.cnt, iters=iters, cfg_filter=cfg_filter)
-            _TABLES[bf][key[:3]] = best
+            if key[4]:                                     # (F(6x6): the persistent kernel only)
+                best = tune_desc(d, bf, p.ws, p.cnt, iters=iters, cfg_filter=lambda k_, c_: c_ >= ops.WINO_GEMM_CFG0 and (cfg_filter is None or cfg_filter(k_, c_)))
+            else:
+                best = tune_desc(d, bf, p.ws, p.cnt, iters=iters, cfg_filter=cfg_filter)
+            table_of(d, bf)[key[:3]] = best
             for l, in_q in launches:
                 l.args = (l.args[0], apply_choice(l.args[0], best, p.ws_q if in_q else p.ws, p.cnt_q if in_q else p.cnt), bf)
         if seen:

@@ -339,32 +339,65 @@ def winograd_rows(N, H, W):
     return (t + WINO_ROW_MULT - 1) // WINO_ROW_MULT * WINO_ROW_MULT
 
 
+# Winograd F(6x6, 3x3) (f32 inference layers; csrc/conv_winograd.hip): points 0, +-1, +-2, +-1/2, inf
+_WINO6_G = torch.tensor([[1, 0, 0], [-2 / 9, -2 / 9, -2 / 9], [-2 / 9, 2 / 9, -2 / 9], [1 / 90, 1 / 45, 2 / 45], [1 / 90, -1 / 45, 2 / 45],
+                         [32 / 45, 16 / 45, 8 / 45], [32 / 45, -16 / 45, 8 / 45], [0, 0, 1]], dtype=torch.float64)
+WINO6_ROW_MULT = 64                   # rows per component are padded to the persistent GEMM's shorter tile (64 x 128, 64 x 64)
+
+
+def pack_winograd6_weight(w):
+    """[Cout, Cin, 3, 3] conv filters -> U [64 * cout_pad, Cin] f32: U[8i+j] = (G g G^T)[i][j] in float64, every product and sum rounded
+    on its own in the order of refresh kind 6 (csrc/refresh.hip), so that the device's image of a parameter equals this one bit for bit."""
+    cout, cin = w.shape[0], w.shape[1]
+    assert tuple(w.shape[2:]) == (3, 3)
+    g, G = w.detach().double().cpu(), _WINO6_G
+    col = lambda k: G[:, k].view(8, 1)
+    tmp = (col(0) * g[:, :, None, 0, :] + col(1) * g[:, :, None, 1, :]) + col(2) * g[:, :, None, 2, :]          # G g: [Cout,Cin,8,3]
+    U = (tmp[..., 0, None] * G[:, 0] + tmp[..., 1, None] * G[:, 1]) + tmp[..., 2, None] * G[:, 2]               # (G g) G^T: [Cout,Cin,8,8]
+    cp = (cout + 255) // 256 * 256
+    out = torch.zeros(64, cp, cin, dtype=torch.float32)
+    out[:, :cout] = U.permute(2, 3, 0, 1).reshape(64, cout, cin).float()
+    return out.reshape(64 * cp, cin).contiguous()
+
+
+def winograd6_tiles(N, H, W):
+    return N * ((H + 5) // 6) * ((W + 5) // 6)
+
+
+def winograd6_rows(N, H, W):
+    return (winograd6_tiles(N, H, W) + WINO6_ROW_MULT - 1) // WINO6_ROW_MULT * WINO6_ROW_MULT
+
+
 def pack_winograd_weight_bf16(w):
     """The 36 transform-domain filter banks (pack_winograd_weight: float64 transform) rounded once to bf16: [36 * cout_pad, Cin] bf16."""
     return pack_winograd_weight(w).to(torch.bfloat16).contiguous()
 
 
-def winograd_input(x, V, rows_pad, relu, N=None, H=None, W=None, cin=None, ld_x=None):
+def winograd_input(x, V, rows_pad, relu, N=None, H=None, W=None, cin=None, ld_x=None, tile=4):
+    """``tile`` = 6: the F(6x6, 3x3) transform (V [64 * rows_pad, cin], f32 only)."""
     if N is None:
         N, H, W = x.shape[0], x.shape[1], x.shape[2]
     cin = cin if cin is not None else x.shape[-1]
     ld_x = ld_x if ld_x is not None else x.shape[-1]
+    if tile == 6:
+        check(_lib.lib().vfn_winograd6_input_f32(ptr(x), N, H, W, cin, ld_x, int(relu), ptr(V), rows_pad, stream()), 'vfn_winograd6_input_f32')
+        return
     if V.dtype == torch.bfloat16:            # the plain-bf16 mode: V written as bf16
         check(_lib.lib().vfn_winograd_input_bf16(ptr(x), N, H, W, cin, ld_x, int(relu), ptr(V), rows_pad, stream()), 'vfn_winograd_input_bf16')
         return
     check(_lib.lib().vfn_winograd_input_f32(ptr(x), N, H, W, cin, ld_x, int(relu), ptr(V), rows_pad, stream()), 'vfn_winograd_input_f32')
 
 
-def winograd_output(Mb, rows_pad, out, N, H, W, cout, scale, shift, res, res_ld, res_mod, relu_out, out_ld=None):
-    check(_lib.lib().vfn_winograd_output_f32(ptr(Mb), rows_pad, N, H, W, cout, ptr(scale), ptr(shift), ptr(res), int(res_ld), int(res_mod),
-                                             int(relu_out), ptr(out), out_ld if out_ld is not None else out.shape[-1], stream()),
-          'vfn_winograd_output_f32')
+def winograd_output(Mb, rows_pad, out, N, H, W, cout, scale, shift, res, res_ld, res_mod, relu_out, out_ld=None, tile=4):
+    name = 'vfn_winograd6_output_f32' if tile == 6 else 'vfn_winograd_output_f32'
+    check(getattr(_lib.lib(), name)(ptr(Mb), rows_pad, N, H, W, cout, ptr(scale), ptr(shift), ptr(res), int(res_ld), int(res_mod),
+                                    int(relu_out), ptr(out), out_ld if out_ld is not None else out.shape[-1], stream()), name)
 
 
-def make_winograd_gemm_desc(V, U, Mb, rows_pad, cin, cout):
-    """The 36 transform-domain GEMMs as one batched-filter launch of the convolution kernels."""
-    d = make_conv_desc(V, U, cout, 1, 1, 1, 0, Mb, None, None, None, False, False, cin=cin, in_ld=cin, out_ld=cout, N=1, H=1, W=36 * rows_pad)
-    d.cout_pad = U.shape[0] // 36
+def make_winograd_gemm_desc(V, U, Mb, rows_pad, cin, cout, comps=36):
+    """The 36 (F(6x6, 3x3): 64) transform-domain GEMMs as one batched-filter launch of the convolution kernels."""
+    d = make_conv_desc(V, U, cout, 1, 1, 1, 0, Mb, None, None, None, False, False, cin=cin, in_ld=cin, out_ld=cout, N=1, H=1, W=comps * rows_pad)
+    d.cout_pad = U.shape[0] // comps
     d.w_batch_rows = rows_pad
     d.k_rot = _WINO_KROT
     return d
@@ -377,23 +410,28 @@ def winograd_gemm(V, U, Mb, rows_pad, cin, cout, cfg=0, wgs=0, comps=36):
           'vfn_winograd_gemm_f32')
 
 
-def conv2d_winograd(x, w, scale=None, shift=None, res=None, relu_in=False, relu_out=False, cfg=2, res_mod=0):
-    """Convenience form for tests: x NHWC, w [Cout,Cin,3,3] (torch layout) -> NHWC output of the 3x3 / stride-1 / pad-1 convolution."""
+def conv2d_winograd(x, w, scale=None, shift=None, res=None, relu_in=False, relu_out=False, cfg=2, res_mod=0, tile=4):
+    """Convenience form for tests: x NHWC, w [Cout,Cin,3,3] (torch layout) -> NHWC output of the 3x3 / stride-1 / pad-1 convolution.
+    ``tile`` = 6: F(6x6, 3x3) (``cfg``: a persistent configuration whose tile height is 64, or a tiled one)."""
     N, H, W, cin = x.shape
     cout = w.shape[0]
-    rows = winograd_rows(N, H, W)
-    U = pack_winograd_weight(w).to(x.device)
-    V = torch.empty(36 * rows, cin, device=x.device, dtype=torch.float32)
-    Mb = torch.empty(36 * rows, cout, device=x.device, dtype=torch.float32)
+    if tile == 6:
+        comps, rows, tiles = 64, winograd6_rows(N, H, W), winograd6_tiles(N, H, W)
+        U = pack_winograd6_weight(w).to(x.device)
+    else:
+        comps, rows, tiles = 36, winograd_rows(N, H, W), vfn_winograd_tiles(N, H, W)
+        U = pack_winograd_weight(w).to(x.device)
+    V = torch.empty(comps * rows, cin, device=x.device, dtype=torch.float32)
+    Mb = torch.empty(comps * rows, cout, device=x.device, dtype=torch.float32)
     out = torch.empty(N, H, W, cout, device=x.device, dtype=torch.float32)
-    if rows > vfn_winograd_tiles(N, H, W):
-        V.view(36, rows, cin)[:, vfn_winograd_tiles(N, H, W):].zero_()
-    winograd_input(x, V, rows, relu_in)
-    d = make_winograd_gemm_desc(V, U, Mb, rows, cin, cout)
+    if rows > tiles and tile != 6:                            # (the F(6x6) input transform zeroes its padding rows itself)
+        V.view(comps, rows, cin)[:, tiles:].zero_()
+    winograd_input(x, V, rows, relu_in, tile=tile)
+    d = make_winograd_gemm_desc(V, U, Mb, rows, cin, cout, comps)
     if conv_cfg_kind(cfg) == 2:
         set_streamk(d, *streamk_scratch(x.device))
     conv2d_launch(d, cfg, 0)
-    winograd_output(Mb, rows, out, N, H, W, cout, scale, shift, res, res.shape[-1] if res is not None else 0, res_mod, relu_out)
+    winograd_output(Mb, rows, out, N, H, W, cout, scale, shift, res, res.shape[-1] if res is not None else 0, res_mod, relu_out, tile=tile)
     return out
 
 

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import check, stream, RefreshFilter, RefreshEpilogue
 
-FORWARD, DGRAD, STEM, TAPS, WINO, WINO_DGRAD = 0, 1, 2, 3, 4, 5
+FORWARD, DGRAD, STEM, TAPS, WINO, WINO_DGRAD, WINO6 = 0, 1, 2, 3, 4, 5, 6
 
 
 def _addr(t):
