@@ -134,6 +134,10 @@ ALL_SYMBOLS = sorted(SIGNATURES)
 # the second part of the ABI (entry points only, no structs): Winograd F(6x6, 3x3), include/vfn_winograd6.h
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_winograd6.h')) as _f:
     SIGNATURES_WINOGRAD6 = parse_header(_f.read())[3]
+# the third part (entry points only, no structs): samples and scores of the image model's validation, include/vfn_image_val.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_image_val.h')) as _f:
+    DEFINES_IMAGE_VAL, _, _, SIGNATURES_IMAGE_VAL = parse_header(_f.read())
+SEG_SCORES_CHUNK, SEG_SCORES_MAX_BLOCKS = DEFINES_IMAGE_VAL['VFN_SEG_SCORES_CHUNK'], DEFINES_IMAGE_VAL['VFN_SEG_SCORES_MAX_BLOCKS']
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
     DEFINES['VFN_TRAIN_AUG_MAX_' + _k] for _k in ('T', 'SIDE', 'OUT', 'OBJ'))
@@ -187,6 +191,8 @@ def lib():
             declare(name)
         for name in SIGNATURES_WINOGRAD6:
             declare(name, SIGNATURES_WINOGRAD6, 'vfn_winograd6.h')
+        for name in SIGNATURES_IMAGE_VAL:
+            declare(name, SIGNATURES_IMAGE_VAL, 'vfn_image_val.h')
         _lib = L
     return _lib
 

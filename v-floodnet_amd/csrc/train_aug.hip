@@ -9,6 +9,7 @@
 // operations in the same order, so the output equals Pillow's in every byte (include/vfn_hip.h states each rule).
 #include "common.h"
 #include "../../include/vfn_hip.h"
+#include "../../include/vfn_image_val.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -402,5 +403,227 @@ extern "C" int vfn_train_aug_label_present(const unsigned char* mask, int H, int
     if (hipMemsetAsync(present, 0, 256, (hipStream_t)stream) != hipSuccess) return VFN_ERR_LAUNCH;
     hipLaunchKernelGGL(label_present_kernel, dim3(cdiv(S * S, 256)), dim3(256), 0, (hipStream_t)stream, mask, xtab, ytab, H, W, S,
                        present);
+    return vfn_check_launch();
+}
+
+// ================================================================================================ one sample of the image module
+// WaterDataset_RGB(mode='train_offline') (image_module/dataset_water.py:136-153): the same Pillow arithmetic composed the image
+// module's way -- colour operations in a fixed order, each optional; the flip AFTER the affine map; the label kept as an index;
+// ImageNet normalisation into a slot of the model's batch.  One photograph per call.  Rules: include/vfn_image_val.h.
+namespace {
+
+struct SampleJit { int bri, con, hue_on, hue; float fb, fc; };
+
+// FINAL = false: brightness (when on), then the sum of L for the contrast step's mean.  FINAL = true: every operation that is on.
+template <bool FINAL>
+__global__ void __launch_bounds__(256) sample_jitter_kernel(const u8* __restrict__ src, u8* __restrict__ jit,
+                                                            unsigned long long* __restrict__ lsum, int n, SampleJit J) {
+    int mean = 0;
+    if (FINAL && J.con) mean = (int)((double)lsum[0] / (double)n + 0.5);
+    int acc = 0;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+        const u8* s = src + (size_t)p * 3;
+        int r = s[0], g = s[1], b = s[2];
+        if (J.bri) r = blend(0, r, J.fb), g = blend(0, g, J.fb), b = blend(0, b, J.fb);
+        if (!FINAL) {
+            acc += luma(r, g, b);
+            continue;
+        }
+        if (J.con) r = blend(mean, r, J.fc), g = blend(mean, g, J.fc), b = blend(mean, b, J.fc);
+        if (J.hue_on) {
+            int hh, ss, vv;
+            rgb2hsv(r, g, b, hh, ss, vv);
+            hsv2rgb((hh + J.hue) & 255, ss, vv, r, g, b);
+        }
+        u8* d = jit + (size_t)p * 3;
+        d[0] = (u8)r, d[1] = (u8)g, d[2] = (u8)b;
+    }
+    if (!FINAL) {
+        acc = wave_sum_i(acc);
+        if ((threadIdx.x & 63) == 0) atomicAdd(lsum, (unsigned long long)acc);
+    }
+}
+
+struct SampleAff { double m[6]; long long fx[6]; int on, flip, tabs; int i, j, h, w; };
+
+// affine_kernel's arithmetic at output column xs = W - 1 - x (flip after the map) or x; the source is read as it lies
+__global__ void __launch_bounds__(256) sample_affine_kernel(const u8* __restrict__ img, const u8* __restrict__ label,
+                                                            const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                                            u8* __restrict__ win_img, u8* __restrict__ win_label, int H, int W,
+                                                            SampleAff F) {
+    const int wx = blockIdx.x * 64 + threadIdx.x, wy = blockIdx.y * 4 + threadIdx.y;
+    if (wx >= F.w || wy >= F.h) return;
+    const int x = F.j + wx, y = F.i + wy;                               // the pixel of the flipped result
+    const int xs = F.flip ? W - 1 - x : x;                              // the output column of the transform under the flip
+    u8* oi = win_img + ((size_t)wy * F.w + wx) * 3;
+    u8* ol = win_label + (size_t)wy * F.w + wx;
+    auto px = [&](int yy, int xx, int c) { return (double)img[((size_t)yy * W + xx) * 3 + c]; };
+    if (!F.on) {
+        const u8* s = img + ((size_t)y * W + xs) * 3;
+        oi[0] = s[0], oi[1] = s[1], oi[2] = s[2];
+        *ol = label[(size_t)y * W + xs];
+        return;
+    }
+    // ---- label: nearest.  Geometry.c affine_fixed (16.16) or, when m1 == m3 == 0, ImagingScaleAffine's index tables
+    int sx, sy;
+    if (F.tabs) {
+        sx = xtab[xs], sy = ytab[y];
+    } else {
+        sx = (int)((F.fx[2] + F.fx[1] * y + F.fx[0] * xs) >> 16);
+        sy = (int)((F.fx[5] + F.fx[4] * y + F.fx[3] * xs) >> 16);
+    }
+    *ol = (sx >= 0 && sx < W && sy >= 0 && sy < H) ? label[(size_t)sy * W + sx] : (u8)0;
+    // ---- image: Geometry.c affine_transform + bicubic_filter8, in double
+    const double xc = xs + 0.5, yc = y + 0.5;
+    double xin = F.m[0] * xc + F.m[1] * yc + F.m[2];
+    double yin = F.m[3] * xc + F.m[4] * yc + F.m[5];
+    if (xin < 0.0 || xin >= (double)W || yin < 0.0 || yin >= (double)H) {
+        oi[0] = oi[1] = oi[2] = 0;
+        return;
+    }
+    xin -= 0.5, yin -= 0.5;
+    const int x0 = (int)floor(xin), y0 = (int)floor(yin);
+    const double dx = xin - x0, dy = yin - y0;
+    int cx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cx[k] = min(max(x0 - 1 + k, 0), W - 1);
+    double v[3][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int yy = y0 - 1 + r;
+        // row y0 - 1 is clamped; a later row outside the image repeats the previous row's interpolated value
+        const bool ok = r == 0 || (yy >= 0 && yy < H);
+        const int yr = min(max(yy, 0), H - 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            v[c][r] = ok ? cubic(px(yr, cx[0], c), px(yr, cx[1], c), px(yr, cx[2], c), px(yr, cx[3], c), dx) : v[c][r - (r > 0)];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double o = cubic(v[c][0], v[c][1], v[c][2], v[c][3], dy);
+        oi[c] = o <= 0.0 ? (u8)0 : o >= 255.0 ? (u8)255 : (u8)(int)o;          // truncated, not rounded
+    }
+}
+
+struct SampleNorm { float mean[3], std[3]; };
+
+// ImagingResampleVertical_8bpc over hpass [h][S][3], then ToTensor + Normalize into dst [3][S][S] (a slot of the batch)
+__global__ void __launch_bounds__(256) sample_resize_v_norm_kernel(const u8* __restrict__ hpass, float* __restrict__ dst,
+                                                                   const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                                   int ksize, int h, int S, SampleNorm nm) {
+    const int ox = blockIdx.x * 64 + threadIdx.x, oy = blockIdx.y * 4 + threadIdx.y;
+    if (ox >= S || oy >= S) return;
+    const int lo = max(bounds[oy * 2], 0), n = min(min(bounds[oy * 2 + 1], ksize), h - lo);
+    const int* k = kk + (size_t)oy * ksize;
+    const u8* in = hpass + ((size_t)lo * S + ox) * 3;
+    int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+    for (int q = 0; q < n; ++q) {
+        const int c = k[q];
+        const u8* p = in + (size_t)q * S * 3;
+        s0 += c * p[0], s1 += c * p[1], s2 += c * p[2];
+    }
+    float* o = dst + (size_t)oy * S + ox;
+    const size_t plane = (size_t)S * S;
+    o[0] = ((float)clip8(s0 >> 22) / 255.0f - nm.mean[0]) / nm.std[0];
+    o[plane] = ((float)clip8(s1 >> 22) / 255.0f - nm.mean[1]) / nm.std[1];
+    o[2 * plane] = ((float)clip8(s2 >> 22) / 255.0f - nm.mean[2]) / nm.std[2];
+}
+
+// Geometry.c ImagingScaleAffine through the host's index tables (-1: outside, the pixel stays 0); the index as a float
+__global__ void __launch_bounds__(256) sample_label_kernel(const u8* __restrict__ plane, float* __restrict__ dst,
+                                                           const int* __restrict__ nx, const int* __restrict__ ny, int h, int w,
+                                                           int S) {
+    const int ox = blockIdx.x * 64 + threadIdx.x, oy = blockIdx.y * 4 + threadIdx.y;
+    if (ox >= S || oy >= S) return;
+    const int xi = nx[ox], yi = ny[oy];
+    const int lab = (xi >= 0 && xi < w && yi >= 0 && yi < h) ? plane[(size_t)yi * w + xi] : 0;
+    dst[(size_t)oy * S + ox] = (float)lab;
+}
+
+bool side_ok(int v) { return v >= 1 && v <= VFN_TRAIN_AUG_MAX_SIDE; }
+bool slot_ok(int B, int b, int S) { return B >= 1 && b >= 0 && b < B && S >= 1 && S <= VFN_TRAIN_AUG_MAX_OUT; }
+
+}  // namespace
+
+extern "C" int vfn_imgval_jitter(const unsigned char* src, int H, int W, int brightness_on, float brightness, int contrast_on,
+                                 float contrast, int hue_on, int hue_shift, unsigned char* jit, unsigned long long* lsum,
+                                 void* stream) {
+    if (!src || !jit || !side_ok(H) || !side_ok(W)) return VFN_ERR_ARG;
+    if (brightness_on && !isfinite(brightness)) return VFN_ERR_ARG;
+    if (contrast_on && (!isfinite(contrast) || !lsum)) return VFN_ERR_ARG;
+    if (hue_on && (hue_shift < 0 || hue_shift > 255)) return VFN_ERR_ARG;
+    if (!brightness_on && !contrast_on && !hue_on) return VFN_OK;
+    SampleJit J = {};
+    J.bri = brightness_on != 0, J.con = contrast_on != 0, J.hue_on = hue_on != 0, J.hue = hue_on ? hue_shift : 0;
+    J.fb = brightness_on ? brightness : 1.0f, J.fc = contrast_on ? contrast : 1.0f;
+    const int n = H * W;
+    const dim3 grid(min(cdiv(n, 256), 1024)), block(256);
+    if (J.con) {
+        if (hipMemsetAsync(lsum, 0, sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return VFN_ERR_LAUNCH;
+        hipLaunchKernelGGL(sample_jitter_kernel<false>, grid, block, 0, (hipStream_t)stream, src, jit, lsum, n, J);
+    }
+    hipLaunchKernelGGL(sample_jitter_kernel<true>, grid, block, 0, (hipStream_t)stream, src, jit, lsum, n, J);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_imgval_affine_window(const unsigned char* img, const unsigned char* label, int H, int W, int affine,
+                                        const double* m, int nearest_tables, const int* xtab, const int* ytab, int flip_after,
+                                        int win_i, int win_j, int win_h, int win_w, unsigned char* win_img,
+                                        unsigned char* win_label, void* stream) {
+    if (!img || !label || !win_img || !win_label || !side_ok(H) || !side_ok(W)) return VFN_ERR_ARG;
+    if (win_i < 0 || win_j < 0 || win_h < 1 || win_w < 1 || win_i > H - win_h || win_j > W - win_w) return VFN_ERR_ARG;
+    SampleAff F = {};
+    F.on = affine != 0, F.flip = flip_after != 0, F.tabs = affine && nearest_tables;
+    F.i = win_i, F.j = win_j, F.h = win_h, F.w = win_w;
+    if (F.on) {
+        if (!m) return VFN_ERR_ARG;
+        for (int k = 0; k < 6; ++k) {
+            if (!isfinite(m[k])) return VFN_ERR_ARG;
+            F.m[k] = m[k];
+        }
+        if (F.tabs && (!xtab || !ytab)) return VFN_ERR_ARG;
+        // Geometry.c check_fixed: the 16.16 path needs every corner coordinate below 32768
+        const double xs[2] = {0.0, (double)W}, ys[2] = {0.0, (double)H};
+        for (int a = 0; a < 2 && !F.tabs; ++a)
+            for (int b = 0; b < 2; ++b)
+                if (!(fabs(m[0] * xs[a] + m[1] * ys[b] + m[2]) < 32768.0 && fabs(m[3] * xs[a] + m[4] * ys[b] + m[5]) < 32768.0))
+                    return VFN_ERR_ARG;
+        auto fix = [](double v) { return (long long)floor(v * 65536.0 + 0.5); };
+        F.fx[0] = fix(m[0]), F.fx[1] = fix(m[1]), F.fx[3] = fix(m[3]), F.fx[4] = fix(m[4]);
+        F.fx[2] = fix(m[2] + m[0] * 0.5 + m[1] * 0.5);
+        F.fx[5] = fix(m[5] + m[3] * 0.5 + m[4] * 0.5);
+    }
+    hipLaunchKernelGGL(sample_affine_kernel, dim3(cdiv(win_w, 64), cdiv(win_h, 4)), dim3(64, 4), 0, (hipStream_t)stream, img, label,
+                       xtab, ytab, win_img, win_label, H, W, F);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_imgval_resize_norm(const unsigned char* win_img, int h, int w, unsigned char* hpass, const int* kx_bounds,
+                                      const int* kx, int ksize_x, const int* ky_bounds, const int* ky, int ksize_y, float* x, int B,
+                                      int b, int S, const float* mean, const float* std, void* stream) {
+    if (!win_img || !hpass || !kx_bounds || !kx || !ky_bounds || !ky || !x || !mean || !std || !side_ok(h) || !side_ok(w) ||
+        !slot_ok(B, b, S) || ksize_x < 1 || ksize_y < 1)
+        return VFN_ERR_ARG;
+    SampleNorm nm;
+    for (int c = 0; c < 3; ++c) {
+        nm.mean[c] = mean[c], nm.std[c] = std[c];
+        if (!isfinite(mean[c]) || !isfinite(std[c]) || std[c] == 0.f) return VFN_ERR_ARG;
+    }
+    ResArgs A = {};
+    A.h[0] = h, A.w[0] = w;
+    const dim3 block(64, 4);
+    // (the clip's horizontal pass with T = 1: frame 0 starts at the buffer's first byte whatever H and W are)
+    hipLaunchKernelGGL(resize_h_kernel, dim3(cdiv(S, 64), cdiv(h, 4), 1), block, 0, (hipStream_t)stream, win_img, hpass, kx_bounds, kx,
+                       ksize_x, h, w, S, A);
+    hipLaunchKernelGGL(sample_resize_v_norm_kernel, dim3(cdiv(S, 64), cdiv(S, 4)), block, 0, (hipStream_t)stream, hpass,
+                       x + (size_t)b * 3 * S * S, ky_bounds, ky, ksize_y, h, S, nm);
+    return vfn_check_launch();
+}
+
+extern "C" int vfn_imgval_label_gather(const unsigned char* plane, int h, int w, const int* nx, const int* ny, float* y, int B, int b,
+                                       int S, void* stream) {
+    if (!plane || !nx || !ny || !y || !side_ok(h) || !side_ok(w) || !slot_ok(B, b, S)) return VFN_ERR_ARG;
+    hipLaunchKernelGGL(sample_label_kernel, dim3(cdiv(S, 64), cdiv(S, 4)), dim3(64, 4), 0, (hipStream_t)stream, plane,
+                       y + (size_t)b * S * S, nx, ny, h, w, S);
     return vfn_check_launch();
 }
