@@ -36,10 +36,12 @@ for lname, lst in lists.items():
         cfg = ''
         if l.fn is ops.conv2d_launch:
             if l.args[1] >= ops.WINO_GEMM_CFG0:          # the persistent transform-domain GEMM: tile / request depth / workgroups
-                c_ = l.args[1] - (ops.PCONV_CFG0 if l.args[1] >= ops.PCONV_CFG0 else ops.WINO_GEMM_CFG0)
-                cfg = 'p%dx%d/pd%d/%d' % (ops.WINO_GEMM_TILES[c_ & 3][0], ops.WINO_GEMM_TILES[c_ & 3][1], 1 + ((c_ & 7) >> 2), (c_ >> 3) * 128)
+                bm_, bn_, _, _, pd_, wgs_ = ops.persistent_cfg_info(l.args[1])
+                cfg = 'p%dx%d/pd%d/%d' % (bm_, bn_, pd_, wgs_)
             else:
                 cfg = '%dx%d' % tiles[l.args[1]] + ('/k%d' % l.args[0].ksplit if l.args[0].ksplit > 1 else '') + ('/wk%d' % ops.conv_cfg_wk(l.args[1]) if ops.conv_cfg_wk(l.args[1]) > 1 else '')
+        elif l.fn is ops.shortcut_fused_launch:          # a block's shortcut inside conv3's launch: tile / request depth / workgroups
+            cfg = 'f%dx%d/pd1/%d' % (ops.WINO_GEMM_TILES[l.args[2]][:2] + (l.args[3],))
         tf = l.flops / us / 1e6 if l.flops else 0
         rows.append((lname, l.name, cfg, us, tf))
         t = tot.setdefault(lname, [0.0, 0.0]); t[0] += us; t[1] += l.flops

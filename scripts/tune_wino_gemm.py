@@ -3,6 +3,12 @@ C2 / C3 / C5 plans (and of the training plan) now that the persistent kernel (vf
 vfn_conv1x1_persistent_f32, ids >= 2000) competes with one-workgroup-per-tile launches: the table entry of a shape changes hands only
 when the new choice is at least MARGIN faster than the old one, re-timed alternately.
 Writes gpurun_out/tuned_gfx950.json + gpurun_out/r05_tune_{wino_gemm,pconv}_report.json."""
+# Argument `rows32`: every F(6x6) GEMM of the inference plans whose rows shrink when padded to 32 instead of 64, through the 32-row tiles
+# against its shipped 64-row choice -> tuned_gfx950_wino6.json gains (64 * rows32, Cout, Cin) where 32 rows are MARGIN faster.
+# Argument `shortcut`: every fused shortcut launch (ops.shortcut_fused_launch) of the inference plans through the persistent kernel's
+# configurations -> tuned_gfx950_shortcut.json (a shape whose best fused time does not beat its two launches in
+# scripts/profile_layers.py's table gets tile cfg -1 there by hand: it keeps two launches).  Both write the table and
+# tune_{rows32,shortcut}_report.json into the directory VFN_TUNE_OUT names (default tune_out/, as scripts/tune_winograd.py).
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, vfloodnet_amd
@@ -32,8 +38,81 @@ def timeit(d, c, iters=12):
     return best * 1e3
 
 
+def time_call(fn, iters=12):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    best = None
+    for _ in range(4):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        best = ms if best is None else min(best, ms)
+    return best * 1e3
+
+
+def tune_rows32(plans):
+    """The F(6x6) GEMMs on operands of their own (the timing does not depend on the values): shipped 64-row choice against every
+    32-row configuration on the 32-padded rows."""
+    seen = {}
+    for p in plans:
+        for lst in p.all_lists():
+            for i, l in enumerate(lst):
+                if l.fn is ops.conv2d_launch and engine.is_wino6_desc(l.args[0]) and i > 0 and lst[i - 1].fn is ops.winograd_input:
+                    d, (N, H, W) = l.args[0], lst[i - 1].args[4:7]
+                    rows32 = (ops.winograd6_tiles(N, H, W) + 31) // 32 * 32
+                    if rows32 < d.w_batch_rows and d.w_batch_rows % 64 == 0:
+                        seen.setdefault((d.w_batch_rows, rows32, d.Cout, d.Cin, d.cout_pad), (l.name, l.args[1]))
+    for (rows, rows32, cout, cin, cout_pad), (name, old) in sorted(seen.items()):
+        V, U = torch.randn(64 * rows, cin, device=dev), torch.randn(64 * cout_pad, cin, device=dev)
+        Mb = torch.empty(64 * rows, cout, device=dev)
+        d64 = ops.make_winograd_gemm_desc(V, U, Mb, rows, cin, cout, 64)
+        d32 = ops.make_winograd_gemm_desc(V[:64 * rows32], U, Mb[:64 * rows32], rows32, cin, cout, 64)
+        cand = sorted((time_call(lambda: ops.conv2d_launch(d32, c, 0), 6), c) for c in ops.wino_gemm_cfg_options(rows32, cout)
+                      if ops.is_wino_gemm32_cfg(c))
+        t_old = time_call(lambda: ops.conv2d_launch(d64, old, 0))
+        best = min((time_call(lambda: ops.conv2d_launch(d32, c, 0)), c) for _, c in cand[:3])
+        t_old = min(t_old, time_call(lambda: ops.conv2d_launch(d64, old, 0)))
+        take = best[0] < MARGIN * t_old
+        report.append({'layer': name, 'rows': rows, 'rows32': rows32, 'cout': cout, 'cin': cin, 'old': old, 'old_us': round(t_old, 1),
+                       'new': best[1], 'new_cfg': list(ops.persistent_cfg_info(best[1])), 'new_us': round(best[0], 1), 'taken': bool(take)})
+        print(report[-1], flush=True)
+        if take:
+            engine._TUNED_WINO6[(64 * rows32, cout, cin)] = (best[1], 1, 0)
+    engine.save_tuned(OUT + '/tuned_gfx950_wino6.json', 'wino6')
+
+
+def tune_shortcut(plans):
+    seen = {}
+    for p in plans:
+        for lst in p.all_lists():
+            for l in lst:
+                if l.fn is ops.shortcut_fused_launch:
+                    sc, d = l.args[:2]
+                    seen.setdefault((d.M, d.Cout, sc.Cin, d.Cin), l)
+    for key, l in sorted(seen.items()):
+        sc, d = l.args[:2]
+        cand = sorted((time_call(lambda: ops.shortcut_fused_launch(sc, d, *o), 6), o) for o in ops.shortcut_fused_cfg_options(sc, d))
+        best = min((time_call(lambda: ops.shortcut_fused_launch(sc, d, *o)), o) for _, o in cand[:3])
+        t_cur = time_call(lambda: ops.shortcut_fused_launch(sc, d, *l.args[2:4]))
+        report.append({'layer': l.name, 'shape': list(key), 'current': list(l.args[2:4]), 'current_us': round(t_cur, 1), 'best': list(best[1]),
+                       'best_us': round(best[0], 1), 'all_us': {'%d/%d' % o: round(t, 1) for t, o in cand}})
+        print(report[-1], flush=True)
+        engine._TUNED_SHORTCUT[key] = tuple(best[1])
+    engine.save_tuned(OUT + '/tuned_gfx950_shortcut.json', 'shortcut')
+
+
 seen = {}
 plans = [eng.plan(h, w, 2) for (h, w) in [(480, 854), (480, 853)]]
+if WHICH in ('rows32', 'shortcut'):
+    OUT = os.environ.get('VFN_TUNE_OUT', 'tune_out')
+    os.makedirs(OUT, exist_ok=True)
+    (tune_rows32 if WHICH == 'rows32' else tune_shortcut)(plans)
+    json.dump(report, open(OUT + '/tune_%s_report.json' % WHICH, 'w'), indent=1)
+    sys.exit(0)
 if os.environ.get('VFN_TUNE_TRAIN', '1') == '1':
     try:
         tp = eng.plan(400, 400, 2, keep_acts=True)
@@ -52,7 +131,7 @@ for p in plans:
 for key, (d, p) in sorted(seen.items()):
     old = table.get(key) or engine.choose_cfg(*key, 0)
     cand = []
-    for c in (ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout) if WHICH == 'wino' else ops.pconv_cfg_options(d.Cout)):
+    for c in (ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout, rows32=False) if WHICH == 'wino' else ops.pconv_cfg_options(d.Cout)):
         engine.apply_choice(d, (c, 1, 0), p.ws, p.cnt)
         try:
             cand.append((timeit(d, c, 6), c))

@@ -54,7 +54,7 @@ def measure_f6(p, l, d, layer, key):
         dg = seq[1].args[0]
         if tile == 6:
             best, t_best = None, None
-            for c in ops.wino_gemm_cfg_options(dg.w_batch_rows, dg.Cout):
+            for c in ops.wino_gemm_cfg_options(dg.w_batch_rows, dg.Cout, rows32=False):
                 engine.apply_choice(dg, (c, 1, 0), p.ws, p.cnt)
                 t = time_list([engine.Launch(ops.conv2d_launch, (dg, c, 0), 'g')], iters=5)
                 if t_best is None or t < t_best:
@@ -112,7 +112,7 @@ for (h, w) in sizes:
             dg = seq[1].args[0]
             gkey = (dg.M, dg.Cout, dg.KH * dg.KW * dg.Cin)
             best, t_best = None, None
-            for c in ops.wino_gemm_cfg_options(dg.w_batch_rows, dg.Cout):        # the persistent GEMM (round 5)
+            for c in ops.wino_gemm_cfg_options(dg.w_batch_rows, dg.Cout, rows32=False):        # the persistent GEMM (round 5)
                 try:
                     engine.apply_choice(dg, (c, 1, 0), p.ws, p.cnt)
                     t = time_list([engine.Launch(ops.conv2d_launch, (dg, c, MODE), 'g')], iters=5)

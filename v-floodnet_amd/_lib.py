@@ -26,12 +26,13 @@ _RENAMED = {'in': 'inp'}   # field names that are Python keywords
 _DECLARATOR = re.compile(r'(?:const\s+)?([A-Za-z_][\w ]*?)(?:\s*(\*)\s*|\s+)(\w+)\s*(?:\[([^\]]*)\])?')
 
 
-def parse_header(text):
+def parse_header(text, known_structs=None):
     """``(defines, enums, structs, prototypes)`` of a header in the style of ``include/vfn_hip.h``: the integer ``#define``s
     and ``enum`` values by name, a ``ctypes.Structure`` per ``typedef struct`` and the ``argtypes`` of every ``int vfn_*(...)``.
     Anything else -- an unknown base type, an array bound that does not evaluate, an unbalanced declaration -- is a
-    ``RuntimeError`` that names the declaration; nothing is skipped."""
-    defines, enums, structs, protos = {}, {}, {}, {}
+    ``RuntimeError`` that names the declaration; nothing is skipped.  ``known_structs``: the structs of a header this one builds on
+    (a later part of the ABI that takes descriptors of ``vfn_hip.h``); they are not returned again."""
+    defines, enums, structs, protos = {}, {}, dict(known_structs or {}), {}
 
     def fail(why, decl):
         raise RuntimeError(f'vfn_hip.h: {why}: {" ".join(decl.split())[:120]!r}')
@@ -125,7 +126,7 @@ def parse_header(text):
             protos[m.group(1)] = [] if params == 'void' else [declarator(p, decl, True)[1] for p in params.split(',')]
             continue
         fail('declaration not understood', decl)
-    return defines, enums, structs, protos
+    return defines, enums, {k: v for k, v in structs.items() if k not in (known_structs or {})}, protos
 
 
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_hip.h')) as _f:
@@ -137,6 +138,10 @@ with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_winograd6.h')) as
 # the third part (entry points only, no structs): samples and scores of the image model's validation, include/vfn_image_val.h
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_image_val.h')) as _f:
     DEFINES_IMAGE_VAL, _, _, SIGNATURES_IMAGE_VAL = parse_header(_f.read())
+# the fourth part (entry points only, on the descriptors of vfn_hip.h): a block's shortcut convolution inside conv3's launch,
+# include/vfn_shortcut_fused.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_shortcut_fused.h')) as _f:
+    SIGNATURES_SHORTCUT_FUSED = parse_header(_f.read(), STRUCTS)[3]
 SEG_SCORES_CHUNK, SEG_SCORES_MAX_BLOCKS = DEFINES_IMAGE_VAL['VFN_SEG_SCORES_CHUNK'], DEFINES_IMAGE_VAL['VFN_SEG_SCORES_MAX_BLOCKS']
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
@@ -193,6 +198,8 @@ def lib():
             declare(name, SIGNATURES_WINOGRAD6, 'vfn_winograd6.h')
         for name in SIGNATURES_IMAGE_VAL:
             declare(name, SIGNATURES_IMAGE_VAL, 'vfn_image_val.h')
+        for name in SIGNATURES_SHORTCUT_FUSED:
+            declare(name, SIGNATURES_SHORTCUT_FUSED, 'vfn_shortcut_fused.h')
         _lib = L
     return _lib
 

@@ -17,6 +17,7 @@
 #include "conv_internal.h"
 #include "../../include/vfn_hip.h"
 #include "../../include/vfn_winograd6.h"
+#include "../../include/vfn_shortcut_fused.h"
 
 namespace {
 
@@ -483,239 +484,44 @@ struct wino_gemm_args {
     const float* res;
 };
 
+// DUAL form (CONV only: a block's shortcut 1x1 convolution inside conv3's launch, vfn_conv1x1_shortcut_fused_f32): a unit walks the K
+// tiles of the shortcut source first -- input V [N][H][W][a_ld] sampled at (stride * yo, stride * xo) for output pixel (n, yo, xo) of
+// an Ho x Wo map, filters U [cout_pad][C] -- turns its accumulators into r = acc * scale + shift (floored at 0 when relu_mid) in
+// registers, and walks the main source from zero accumulators; the epilogue adds r where the one-source form loads `res`
+struct wino_dual_args {
+    const float* V;
+    const float* U;
+    const float* scale;
+    const float* shift;
+    int C, a_ld, cout_pad, relu_in, relu_mid, stride, H, W, Ho, Wo, pix;      // (pix = N * H * W input pixels)
+};
+
+// The two kernels share one body, wino_gemm_body.inc, as text: BM .. LP, DUAL, the arguments p and (DUAL) q2 are what it names.  The
+// one-source kernel keeps its signature, its name and -- every DUAL statement being discarded -- its code.
 // LP: both operands are bf16 in memory (V from winograd_input_kernel<true>, U packed by the host): a K tile is 64 channels -- the same
 // 128-byte LDS rows, the same staging -- and a 16-byte fragment is one v_mfma_f32_32x32x16_bf16 (k = 16 kk + 8 h .. + 7), f32 accumulate
 template <int BM, int BN, int WM, int WN, int PD, bool CONV = false, bool LP = false>
 __global__ __launch_bounds__(WM * WN * 64)
 void wino_gemm_kernel(const wino_gemm_args p) {
-    static_assert(!(CONV && LP), "the reduced-precision form is the transform-domain GEMM only");
-    constexpr int BK = 32;                               // floats per LDS row (128 bytes = 32 f32 / 64 bf16)
-    constexpr int KT = LP ? 64 : 32;                     // K elements per tile
-    constexpr int ES = LP ? 2 : 4;                       // bytes per operand element
-    constexpr int NT = WM * WN * 64;
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int AC = BM * 8 / NT, BC = BN * 8 / NT, RSTEP = NT / 8;
-    static_assert(AC >= 1 && BC >= 1, "tile too small for the thread count");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sA = reinterpret_cast<float*>(smem);          // [2][BM][32]
-    float* sB = sA + 2 * BM * BK;                        // [2][BN][32]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int li = lane & 31, lh = lane >> 5;
-
-    // units of this workgroup: XCD x (= blockIdx % 8) owns one contiguous run of the unit list (filter tile fastest, then row
-    // tile, then component: the workgroups of one XCD share operand tiles through its L2), dealt round-robin to its workgroups
-    const int per = p.mtiles * p.ntiles, total = p.comps * per;
-    const int gx = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int q = total >> 3, r8 = total & 7;
-    const int u_begin = xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q;
-    const int u_end = u_begin + q + (xcd < r8 ? 1 : 0);
-    const int first = u_begin + loc;
-    const int n_units = first < u_end ? (u_end - first + gx - 1) / gx : 0;
-    const int nk = p.C / KT;
-    const int T = n_units * nk;
-    if (T == 0) return;
-
-    const int c16 = tid & 7, r0 = tid >> 3;
-    const int a_ld = CONV ? p.a_ld : p.C;
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.V), 0, (int)((size_t)p.comps * p.rows_pad * a_ld * ES), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.U), 0, (int)((size_t)p.comps * p.cout_pad * p.C * ES), 0x00020000);
-    int a_thr[AC], b_thr[BC];
-#pragma unroll
-    for (int j = 0; j < AC; ++j) a_thr[j] = (r0 + j * RSTEP) * a_ld * ES + c16 * 16;
-#pragma unroll
-    for (int j = 0; j < BC; ++j) b_thr[j] = (r0 + j * RSTEP) * p.C * ES + c16 * 16;
-
-    // the tile being requested: (unit, K tile) and its operand bases (wave-uniform)
-    int lu = 0, lkt = 0, la_base = 0, lb_base = 0;
-    int n0_cur = 0;
-    auto unit_bases = [&](int ui, int& a_base, int& b_base, size_t& o_base, int* n0 = nullptr) {
-        const int u = first + ui * gx;
-        const int xi = u / per, rem = u - xi * per;
-        const int mt = rem / p.ntiles, nt = rem - mt * p.ntiles;
-        a_base = (xi * p.rows_pad + mt * BM) * a_ld * ES;
-        b_base = (xi * p.cout_pad + nt * BN) * p.C * ES;
-        o_base = CONV ? (size_t)mt * BM : ((size_t)xi * p.rows_pad + mt * BM) * p.Cout + nt * BN;      // (CONV: the first row of the tile)
-        if (n0) *n0 = nt * BN;
-    };
-    size_t o_dummy;
-    unit_bases(0, la_base, lb_base, o_dummy);
-    f32x4 ra[PD][AC], rb[PD][BC];
-    auto request = [&](int slot) {                         // global loads of the next tile in line into staging slot `slot`
-        const int koff = lkt * 128;                        // (a K tile is 128 bytes of every operand row in either arithmetic)
-#pragma unroll
-        for (int j = 0; j < AC; ++j)
-            ra[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsV, a_thr[j], la_base + koff, 0));
-#pragma unroll
-        for (int j = 0; j < BC; ++j)
-            rb[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsU, b_thr[j], lb_base + koff, 0));
-        if (++lkt == nk) {
-            lkt = 0;
-            if (++lu < n_units) unit_bases(lu, la_base, lb_base, o_dummy);
-        }
-    };
-    const float relu_floor = (CONV && p.relu_in) ? 0.f : -INFINITY;
-    auto stage = [&](int buf, int slot) {                  // staging slot -> LDS image (XOR-swizzled 16-byte chunks)
-        float* dA = sA + buf * BM * BK;
-        float* dB = sB + buf * BN * BK;
-#pragma unroll
-        for (int j = 0; j < AC; ++j) {
-            const int r = r0 + j * RSTEP;
-            f32x4 v = ra[slot][j];
-            if constexpr (CONV) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], relu_floor);
-            }
-            *reinterpret_cast<f32x4*>(dA + r * BK + ((c16 ^ ((r >> 1) & 7)) << 2)) = v;
-        }
-#pragma unroll
-        for (int j = 0; j < BC; ++j) {
-            const int r = r0 + j * RSTEP;
-            *reinterpret_cast<f32x4*>(dB + r * BK + ((c16 ^ ((r >> 1) & 7)) << 2)) = rb[slot][j];
-        }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // the unit being multiplied
-    int cu = 0, ckt = 0, ca_dummy, cb_dummy;
-    size_t o_base;
-    unit_bases(0, ca_dummy, cb_dummy, o_base, &n0_cur);
-
-#pragma unroll
-    for (int d = 0; d < PD; ++d)
-        if (d < T) request(d);
-    stage(0, 0);
-    __syncthreads();
-
-    for (int t0 = 0; t0 < T; t0 += PD) {
-#pragma unroll
-        for (int uu = 0; uu < PD; ++uu) {
-            const int t = t0 + uu;
-            if (t >= T) break;
-            const int buf = t & 1;
-            const bool more = t + 1 < T;                   // tile t+1 goes to LDS during this tile (from slot (uu + 1) % PD)
-            const bool more_req = t + PD < T;              // tile t+PD is requested during this tile (into slot uu, free by now)
-            const float* cA = sA + buf * BM * BK + (wm * TM * 32) * BK;
-            const float* cB = sB + buf * BN * BK + (wn * TN * 32) * BK;
-            auto read_frags = [&](int kk, f32x4 (&a)[TM], f32x4 (&b)[TN]) {
-                const int lc = 2 * kk + lh;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int r = i * 32 + li;
-                    a[i] = *reinterpret_cast<const f32x4*>(cA + r * BK + ((lc ^ ((r >> 1) & 7)) << 2));
-                }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int r = j * 32 + li;
-                    b[j] = *reinterpret_cast<const f32x4*>(cB + r * BK + ((lc ^ ((r >> 1) & 7)) << 2));
-                }
-            };
-            f32x4 fa[2][TM], fb[2][TN];
-            read_frags(0, fa[0], fb[0]);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                if (PD > 1 && kk == 0 && more) stage(buf ^ 1, (uu + 1) % PD);       // (requested a whole tile ago: landed)
-                if (kk == 1 && more_req) request(uu);
-                if (PD == 1 && kk == 3 && more) stage(buf ^ 1, 0);
-                if (kk + 1 < 4) read_frags(kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1]);
-                if constexpr (LP) {
-                    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_, fa[kk & 1][i]), __builtin_bit_cast(bf16x8_, fb[kk & 1][j]),
-                                                                                acc[i][j], 0, 0, 0);
-                } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk & 1][i][e], fb[kk & 1][j][e], acc[i][j], 0, 0, 0);
-                }
-            }
-            if (++ckt == nk) {
-                // the unit is complete: lane = filter column (lane & 31), registers = rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-                if constexpr (CONV) {
-                    // y = act(acc * scale[c] + shift[c] + res): lane = channel, so scale / shift are one value per lane and column tile;
-                    // the residual taps of the whole tile are requested first (buffer loads: rows past M / columns past Cout return
-                    // zeros), the stores of invalid positions are dropped by the hardware
-                    const int m0 = (int)o_base;
-                    const int npix = p.rows_pad;
-                    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.Mb, 0, (int)((size_t)npix * p.out_ld * 4), 0x00020000);
-                    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.V), 0,
-                        p.res ? (int)((size_t)(p.res_mod > 0 ? p.res_mod : npix) * p.res_ld * 4) : 0, 0x00020000);
-                    const float floor_ = p.relu_out ? 0.f : -INFINITY;
-                    float rv[TM][TN][16];
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const int col = n0_cur + (wn * TN + j) * 32 + li;
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int row = m0 + (wm * TM + i) * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
-                                const int rrow = p.res_mod > 0 ? row % p.res_mod : row;
-                                rv[i][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                    rsr, (row < npix && col < p.Cout) ? (rrow * p.res_ld + col) * 4 : 0x7ffffff0, 0, 0));
-                            }
-                    }
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const int col = n0_cur + (wn * TN + j) * 32 + li;
-                        const bool cok = col < p.Cout;
-                        const float sc = (p.scale && cok) ? p.scale[col] : 1.f;
-                        const float sh = (p.shift && cok) ? p.shift[col] : 0.f;
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int row = m0 + (wm * TM + i) * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
-                                const float v = vfn_floor_nan(acc[i][j][r] * sc + sh + rv[i][j][r], floor_);
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rso,
-                                                                      (row < npix && cok) ? (row * p.out_ld + col) * 4 : 0x7ffffff0, 0, 0);
-                                acc[i][j][r] = 0.f;
-                            }
-                    }
-                } else {
-                float* o = p.Mb + o_base;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int col = (wn * TN + j) * 32 + li;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        const int rbase = (wm * TM + i) * 32 + 4 * lh;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            if (n0_cur + col < p.Cout)
-                                o[(size_t)(rbase + (r & 3) + 8 * (r >> 2)) * p.Cout + col] = acc[i][j][r];
-                            acc[i][j][r] = 0.f;
-                        }
-                    }
-                }
-                }
-                ckt = 0;
-                if (++cu < n_units) unit_bases(cu, ca_dummy, cb_dummy, o_base, &n0_cur);
-            }
-            __syncthreads();
-        }
-    }
+    constexpr bool DUAL = false;
+    constexpr wino_dual_args q2{};
+#include "wino_gemm_body.inc"
 }
 
-template <int BM, int BN, int WM, int WN, int PD, bool CONV, bool LP>
-int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s) {
+template <int BM, int BN, int WM, int WN, int PD>
+__global__ __launch_bounds__(WM * WN * 64)
+void wino_gemm_dual_kernel(const wino_gemm_args p, const wino_dual_args q2) {
+    constexpr bool DUAL = true, CONV = true, LP = false;
+#include "wino_gemm_body.inc"
+}
+
+template <int BM, int BN, int WM, int WN, int PD, bool CONV, bool LP, bool DUAL = false>
+int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s, const wino_dual_args* dual = nullptr) {
     constexpr size_t lds = 2 * (size_t)(BM + BN) * 32 * sizeof(float);
-    static const bool lds_ready = vfn_allow_lds(&wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>, lds);
+    static const bool lds_ready = [] {
+        if constexpr (DUAL) return vfn_allow_lds(&wino_gemm_dual_kernel<BM, BN, WM, WN, PD>, lds);
+        else return vfn_allow_lds(&wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>, lds);
+    }();
     (void)lds_ready;
     wino_gemm_args p = a;
     p.mtiles = (a.rows_pad + BM - 1) / BM;
@@ -724,7 +530,10 @@ int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s) {
     int grid = wgs > 0 ? wgs : 512;
     if (grid > total) grid = total;
     grid = (grid + 7) / 8 * 8;                              // (the kernel deals units to blockIdx & 7 = XCD, blockIdx >> 3 = slot)
-    hipLaunchKernelGGL((wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>), dim3(grid), dim3(WM * WN * 64), lds, s, p);
+    if constexpr (DUAL)
+        hipLaunchKernelGGL((wino_gemm_dual_kernel<BM, BN, WM, WN, PD>), dim3(grid), dim3(WM * WN * 64), lds, s, p, *dual);
+    else
+        hipLaunchKernelGGL((wino_gemm_kernel<BM, BN, WM, WN, PD, CONV, LP>), dim3(grid), dim3(WM * WN * 64), lds, s, p);
     return vfn_check_launch();
 }
 
@@ -733,13 +542,34 @@ int launch_wino_gemm(const wino_gemm_args& a, int wgs, hipStream_t s) {
 constexpr int kWinoTile[4][4] = {{128, 128, 4, 2}, {64, 128, 2, 4}, {128, 64, 4, 2}, {64, 64, 2, 2}};
 constexpr int kWinoCfgs = 8;
 
-template <bool CONV, bool LP>
-int launch_wino_cfg(const wino_gemm_args& a, int cfg, int wgs, hipStream_t s) {
-    return vfn_dispatch<kWinoCfgs>(cfg, [&](auto id) -> int {
+// (the two-source form: PD = 1 alone -- its PD = 2 instantiations keep 192-240 bytes per lane in scratch and measured 1.5-2x slower)
+constexpr int kWinoDualCfgs = 4;
+
+template <bool CONV, bool LP, bool DUAL = false>
+int launch_wino_cfg(const wino_gemm_args& a, int cfg, int wgs, hipStream_t s, const wino_dual_args* dual = nullptr) {
+    return vfn_dispatch<DUAL ? kWinoDualCfgs : kWinoCfgs>(cfg, [&](auto id) -> int {
         constexpr int c = decltype(id)::value;
         constexpr const int* t = kWinoTile[c & 3];
-        return launch_wino_gemm<t[0], t[1], t[2], t[3], 1 + (c >> 2), CONV, LP>(a, wgs, s);
+        return launch_wino_gemm<t[0], t[1], t[2], t[3], 1 + (c >> 2), CONV, LP, DUAL>(a, wgs, s, dual);
     });
+}
+
+// ... and the 32-row tiles of the f32 transform-domain GEMM alone (a 1/16-resolution F(6x6) map of two images is 90 tiles: 96 rows
+// instead of 128): configurations kWinoCfgs + (cfg & 3 = tile, bit 2 = PD), one 32 x 32 MFMA tile per wave
+constexpr int kWinoTile32[2][4] = {{32, 128, 1, 4}, {32, 64, 1, 2}};
+constexpr int kWinoCfgs32 = 8;
+
+inline const int* wino_tile_of(int cfg) { return cfg < kWinoCfgs ? kWinoTile[cfg & 3] : kWinoTile32[cfg & 1]; }
+inline bool wino_cfg32_ok(int cfg) { return cfg >= kWinoCfgs && cfg < kWinoCfgs + kWinoCfgs32 && (cfg & 3) < 2; }
+
+int launch_wino_cfg32(const wino_gemm_args& a, int cfg, int wgs, hipStream_t s) {
+    switch (cfg - kWinoCfgs) {
+        case 0: return launch_wino_gemm<32, 128, 1, 4, 1, false, false>(a, wgs, s);
+        case 1: return launch_wino_gemm<32, 64, 1, 2, 1, false, false>(a, wgs, s);
+        case 4: return launch_wino_gemm<32, 128, 1, 4, 2, false, false>(a, wgs, s);
+        case 5: return launch_wino_gemm<32, 64, 1, 2, 2, false, false>(a, wgs, s);
+    }
+    return VFN_ERR_ARG;
 }
 
 // the transforms address activations through buffer resources with 32-bit byte offsets: every tensor must stay below 2 GiB
@@ -838,11 +668,13 @@ extern "C" int vfn_winograd_dw_f32(const float* dU, int Cout, int Cin, const flo
 // filter count, C a multiple of 32; every operand below 2 GiB (32-bit buffer offsets)
 extern "C" int vfn_winograd_gemm_f32(const float* V, const float* U, float* Mb, int comps, int rows_pad, int C, int Cout, int cout_pad, int cfg,
                                      int wgs, void* stream) {
-    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 32 || C % 32 || Cout < 1 || cout_pad < Cout || cfg < 0 || cfg >= kWinoCfgs) return VFN_ERR_ARG;
-    const int bm = kWinoTile[cfg & 3][0], bn = kWinoTile[cfg & 3][1];
+    if (!V || !U || !Mb || comps < 1 || rows_pad < 1 || C < 32 || C % 32 || Cout < 1 || cout_pad < Cout || cfg < 0 ||
+        (cfg >= kWinoCfgs && !wino_cfg32_ok(cfg))) return VFN_ERR_ARG;
+    const int bm = wino_tile_of(cfg)[0], bn = wino_tile_of(cfg)[1];
     if (rows_pad % bm || cout_pad < (Cout + bn - 1) / bn * bn) return VFN_ERR_ARG;
     if ((long long)comps * rows_pad * C * 4 >= 0x7fffff00LL || (long long)comps * cout_pad * C * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
     wino_gemm_args a{V, U, Mb, comps, rows_pad, C, Cout, cout_pad, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
+    if (cfg >= kWinoCfgs) return launch_wino_cfg32(a, cfg, wgs, (hipStream_t)stream);
     return launch_wino_cfg<false, false>(a, cfg, wgs, (hipStream_t)stream);
 }
 
@@ -865,6 +697,32 @@ extern "C" int vfn_conv1x1_persistent_f32(const vfn_conv_desc* d, int cfg, int w
     wino_gemm_args a{d->in, d->w, d->out, 1, d->M, d->Cin, d->Cout, d->cout_pad, 0, 0,
                      d->in_ld, d->out_ld, d->res ? d->res_ld : 0, d->res_mod, d->relu_in, d->relu_out, d->scale, d->shift, d->res};
     return launch_wino_cfg<true, false>(a, cfg, wgs, (hipStream_t)stream);
+}
+
+// (include/vfn_shortcut_fused.h) a Bottleneck's shortcut convolution inside its conv3's launch: out = act(conv1x1(main) * scale + shift +
+// r), r = conv1x1(sc, stride 1 or 2) * sc.scale + sc.shift, with r kept in the accumulator registers' twins instead of written and
+// read back.  Every output element is the two fmaf chains and the two epilogue expressions of the two layers run one after the other
+// through vfn_conv1x1_persistent_f32 (or vfn_conv2d_nhwc_f32 without split-K).  cfg: 0..3, the tiles of vfn_conv1x1_persistent_f32 with
+// operands requested one K tile ahead; wgs as there.
+extern "C" int vfn_conv1x1_shortcut_fused_f32(const vfn_conv_desc* sc, const vfn_conv_desc* d, int cfg, int wgs, void* stream) {
+    if (!sc || !d || !sc->in || !sc->w || !d->in || !d->w || !d->out || cfg < 0 || cfg >= kWinoDualCfgs) return VFN_ERR_ARG;
+    for (const vfn_conv_desc* l : {sc, d})
+        if (l->KH != 1 || l->KW != 1 || l->pad != 0 || l->mask || l->in_lp || l->out_lp || l->w_packed || l->ksplit > 1 || l->w_batch_rows ||
+            l->res || l->Cin < 32 || l->Cin % 32 || l->in_ld < l->Cin || l->in_ld % 4 || l->N < 1 || l->H < 1 || l->W < 1) return VFN_ERR_ARG;
+    if (d->stride != 1 || (sc->stride != 1 && sc->stride != 2)) return VFN_ERR_ARG;
+    if (d->M < 1 || d->M != d->N * d->H * d->W || sc->Ho != (sc->H - 1) / sc->stride + 1 || sc->Wo != (sc->W - 1) / sc->stride + 1 ||
+        sc->M != sc->N * sc->Ho * sc->Wo || sc->M != d->M || sc->Cout != d->Cout || d->Cout < 1 || d->out_ld < d->Cout) return VFN_ERR_ARG;
+    const int bn = kWinoTile[cfg & 3][1];
+    const int need = (d->Cout + bn - 1) / bn * bn;
+    if (d->cout_pad < need || sc->cout_pad < need) return VFN_ERR_ARG;
+    const long long lim = 0x7fffff00LL, pix2 = (long long)sc->N * sc->H * sc->W;
+    if (pix2 * sc->in_ld * 4 >= lim || (long long)d->M * d->in_ld * 4 >= lim || (long long)d->M * d->out_ld * 4 >= lim ||
+        (long long)d->cout_pad * d->Cin * 4 >= lim || (long long)sc->cout_pad * sc->Cin * 4 >= lim) return VFN_ERR_ARG;
+    wino_gemm_args a{d->in, d->w, d->out, 1, d->M, d->Cin, d->Cout, d->cout_pad, 0, 0,
+                     d->in_ld, d->out_ld, 0, 0, d->relu_in, d->relu_out, d->scale, d->shift, nullptr};
+    const wino_dual_args a2{sc->in, sc->w, sc->scale, sc->shift, sc->Cin, sc->in_ld, sc->cout_pad, sc->relu_in, sc->relu_out, sc->stride,
+                            sc->H, sc->W, sc->Ho, sc->Wo, (int)pix2};
+    return launch_wino_cfg<true, false, true>(a, cfg, wgs, (hipStream_t)stream, &a2);
 }
 
 // (ABI 12) the plain-bf16 mode's Winograd layers (BASELINE configs C3 / C5): the input transform writes V as bf16 (computed in f32, rounded to

@@ -42,6 +42,11 @@ _TABLE_PATHS = (_TUNED_PATH, _TUNED_BF16_PATH, _TUNED_BF16X3_PATH)
 # file: the row counts are multiples of 64, not of 36 x 256, and a shape may coincide with an F(4x4) one whose tile does not divide the rows
 _TUNED_WINO6 = {}
 _TUNED_WINO6_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_wino6.json')
+# a Bottleneck's shortcut convolution inside conv3's launch (ops.shortcut_fused_launch): (M, Cout, shortcut Cin, main Cin) ->
+# (tile cfg 0..3, workgroups) of the persistent kernel, measured per fused shape (scripts/tune_wino_gemm.py shortcut); tile cfg -1: the
+# shape stays two launches (the fused launch did not beat their sum in scripts/profile_layers.py's tables; entered by hand)
+_TUNED_SHORTCUT = {}
+_TUNED_SHORTCUT_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_shortcut.json')
 
 
 def is_wino6_desc(d):
@@ -69,13 +74,20 @@ def _load_tuned():
                 # convolutions, which share the shape key -- apply_choice falls back to the second triple
                 t = (int(v[0]), int(v[1]), int(v[2]) if len(v) > 2 else 0)
                 table[tuple(int(x) for x in k.split(','))] = t + tuple(int(x) for x in v[3:6]) if len(v) >= 6 else t
+    path = _TUNED_SHORTCUT_PATH
+    alt = os.environ.get('VFN_TUNED_DIR')
+    if alt and os.path.isfile(os.path.join(alt, os.path.basename(path))):
+        path = os.path.join(alt, os.path.basename(path))
+    if os.path.isfile(path):
+        for k, v in json.load(open(path)).items():
+            _TUNED_SHORTCUT[tuple(int(x) for x in k.split(','))] = (int(v[0]), int(v[1]))
 
 
 def save_tuned(path=None, mode=0):
-    """``mode`` = 'wino6': the F(6x6, 3x3) GEMMs' table."""
+    """``mode`` = 'wino6': the F(6x6, 3x3) GEMMs' table; 'shortcut': the fused shortcut launches'."""
     import json
-    table = _TUNED_WINO6 if mode == 'wino6' else _TABLES[mode]
-    with open(path or (_TUNED_WINO6_PATH if mode == 'wino6' else _TABLE_PATHS[mode]), 'w') as f:
+    table = _TUNED_WINO6 if mode == 'wino6' else _TUNED_SHORTCUT if mode == 'shortcut' else _TABLES[mode]
+    with open(path or (_TUNED_WINO6_PATH if mode == 'wino6' else _TUNED_SHORTCUT_PATH if mode == 'shortcut' else _TABLE_PATHS[mode]), 'w') as f:
         json.dump({','.join(str(x) for x in k): list(v) for k, v in sorted(table.items())}, f, indent=0)
 
 
@@ -107,6 +119,12 @@ _WINOGRAD = os.environ.get('VFN_WINOGRAD', '1')
 # faster than F(4x4)'s, scripts/tune_winograd.py), 0 = F(4x4) everywhere (A/B runs in one tree), 2 = every Winograd layer that
 # may (tests).  The bf16 modes, training plans and VFN_WINOGRAD=2 keep F(4x4).
 _WINOGRAD_F6 = os.environ.get('VFN_WINOGRAD_F6', '1')
+# 32-row tiles for an F(6x6) layer's GEMMs (rows per component padded to 32 instead of 64: a 1/16-resolution map of two images is 90
+# tiles -- 96 rows instead of 128): 1 (default) = where tuned_gfx950_wino6.json holds a 32-row configuration for the shape with 32-padded
+# rows, 0 = never (A/B runs in one tree), 2 = every F(6x6) layer whose rows shrink (tuning, tests)
+_WINO_ROWS32 = os.environ.get('VFN_WINO_ROWS32', '1')
+# a block's shortcut (`down`) convolution inside its conv3's launch in the f32 inference plans (Plan._trunk): 0 = two launches
+_SHORTCUT_FUSED = os.environ.get('VFN_SHORTCUT_FUSED', '1')
 _WINOGRAD_LP = os.environ.get('VFN_WINOGRAD_LP', '1') == '1'        # Winograd layers in the plain-bf16 mode too (bf16 V / U, vfn_winograd_gemm_bf16)
 _WINOGRAD_MIN_M = int(os.environ.get('VFN_WINOGRAD_MIN_M', 10000))
 _WINO_TABLE = {}
@@ -235,7 +253,7 @@ def tune_desc(d, bf, ws, cnt, iters=3, cfg_filter=None, allow_split=True):
     if d.w_batch_rows > 0 and bf == 1:
         # a transform-domain GEMM of the plain-bf16 mode: its operands ARE bf16 in memory (vfn_winograd_input_bf16), which only the
         # persistent kernel reads -- the tiled bf16 kernels would take them for f32 tensors
-        for c in ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout):
+        for c in ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout, rows32=False):      # (32-row tiles: measured table entries only)
             if cfg_filter is not None and not cfg_filter(key, c):
                 continue
             t = timeit(c)
@@ -244,7 +262,7 @@ def tune_desc(d, bf, ws, cnt, iters=3, cfg_filter=None, allow_split=True):
         return best
     if d.w_batch_rows > 0 and bf == 0 and d.M // d.w_batch_rows * d.w_batch_rows == d.M:
         # a Winograd-domain GEMM: the persistent kernel's configurations compete with the batched-filter launches below
-        for c in ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout):
+        for c in ops.wino_gemm_cfg_options(d.w_batch_rows, d.Cout, rows32=False):      # (32-row tiles: measured table entries only)
             if cfg_filter is not None and not cfg_filter(key, c):
                 continue
             apply_choice(d, (c, 1, 0), ws, cnt)
@@ -696,6 +714,13 @@ class FramePlan:
         with the layer's epilogue (csrc/conv_winograd.hip).  ``tile`` = 6 (f32): F(6x6, 3x3), 64 GEMMs over fewer, larger tiles."""
         comps = 64 if tile == 6 else 36
         rows = ops.winograd6_rows(N, H, Wd) if tile == 6 else ops.winograd_rows(N, H, Wd)
+        if tile == 6 and bf == 0 and _WINO_ROWS32 != '0':
+            # rows padded to 32 where the shape's measured choice is a 32-row tile (both transforms take any rows_pad >= the tiles: the
+            # input transform zeroes the rows past them in the layout of ITS rows_pad, the output transform never reads them)
+            rows32 = (ops.winograd6_tiles(N, H, Wd) + 31) // 32 * 32
+            c32 = _TUNED_WINO6.get((64 * rows32, layer.cout, layer.cin))
+            if rows32 < rows and (_WINO_ROWS32 == '2' or (c32 is not None and ops.is_wino_gemm32_cfg(c32[0]))):
+                rows = rows32
         key = id(self._ws_cur)
         need_v, need_m = comps * rows * layer.cin, comps * rows * layer.cout
         V, Mb = self._wino.get(key, (None, None))
@@ -725,7 +750,8 @@ class FramePlan:
             # measured one; otherwise 64 x 128 / 64 x 64 tiles, operands requested two K tiles ahead)
             choice = _TUNED_WINO6.get((dg.M, layer.cout, layer.cin))
             if choice is None or choice[0] not in ops.wino_gemm_cfg_options(rows, layer.cout):
-                choice = (ops.wino_gemm_cfg(5 if layer.cout >= 128 else 7, 768), 1, 0)
+                choice = ((ops.wino_gemm32_cfg(4 if layer.cout >= 128 else 5, 768) if rows % 64 else           # (VFN_WINO_ROWS32=2 alone)
+                           ops.wino_gemm_cfg(5 if layer.cout >= 128 else 7, 768)), 1, 0)
         else:
             choice = choose_cfg(dg.M, layer.cout, layer.cin, 0)
         cfg = apply_choice(dg, choice, self._ws_cur, self._cnt_cur)
@@ -757,21 +783,51 @@ class FramePlan:
                 self._conv(lst, blk['conv1'], x, t1, N, H, Wd, relu_out=True, name=nm + '.conv1', lp_out='plain', f32_out=False)
                 self._conv(lst, blk['conv2'], t1, t2, N, H, Wd, relu_out=True, name=nm + '.conv2', lp_out='plain',
                            f32_out=False)
-                if 'down' in blk:
+                out = lb['out'] if bi == len(blocks) - 1 else lb['o'][bi % 2]
+                if self.keep_acts and bi != len(blocks) - 1:
+                    out = torch.empty_like(out)
+                if 'down' in blk and self._shortcut_fused(lst, blk, x, t2, out, N, H, Wd, Ho, Wo, nm):
+                    idn = None                            # (the shortcut tensor never exists: it lives in conv3's registers)
+                elif 'down' in blk:
                     self._conv(lst, blk['down'], x, ds_buf, N, H, Wd, name=nm + '.down')
                     idn = ds_buf
                 else:
                     idn = x
-                out = lb['out'] if bi == len(blocks) - 1 else lb['o'][bi % 2]
-                if self.keep_acts and bi != len(blocks) - 1:
-                    out = torch.empty_like(out)
-                self._conv(lst, blk['conv3'], t2, out, N, Ho, Wo, res=idn, relu_out=True, name=nm + '.conv3',
-                           lp_out='plain')
+                if idn is not None:
+                    self._conv(lst, blk['conv3'], t2, out, N, Ho, Wo, res=idn, relu_out=True, name=nm + '.conv3',
+                               lp_out='plain')
                 if self.keep_acts and acts is not None:
                     acts[(lname, bi)] = dict(x=x, t1=t1, t2=t2, ds=ds_buf if 'down' in blk else None, out=out, stride=s, H=H, W=Wd)
                 x = out
                 H, Wd = Ho, Wo
         return x
+
+    def _shortcut_fused(self, lst, blk, x, t2, out, N, H, Wd, Ho, Wo, nm):
+        """f32 inference plans: the block's `down` convolution (1x1, stride 1 or 2, BN, no ReLU) and its conv3 (1x1, BN, + shortcut,
+        ReLU) as ONE launch of the persistent kernel (ops.shortcut_fused_launch): the shortcut's output stays in registers.  Bit-identical
+        to the two layers run without split-K.  False: the pair is not eligible -> two launches."""
+        down, conv3 = blk['down'], blk['conv3']
+        if (_SHORTCUT_FUSED == '0' or self.keep_acts or self.eng.layer_mode(nm + '.down') != 0 or self.eng.layer_mode(nm + '.conv3') != 0 or
+                x.shape[-1] != down.cin or t2.shape[-1] != conv3.cin):
+            return False
+        sc = ops.make_conv_desc(x, down.w, down.cout, down.k, down.k, down.stride, down.pad, None, down.scale, down.shift,
+                                cin=down.cin, out_ld=down.cout, N=N, H=H, W=Wd)
+        d = ops.make_conv_desc(t2, conv3.w, conv3.cout, conv3.k, conv3.k, conv3.stride, conv3.pad, out, conv3.scale, conv3.shift,
+                               relu_out=True, cin=conv3.cin, N=N, H=Ho, W=Wo)
+        if not ops.shortcut_fused_eligible(sc, d, 0):
+            return False
+        options = ops.shortcut_fused_cfg_options(sc, d)
+        choice = _TUNED_SHORTCUT.get((d.M, d.Cout, sc.Cin, d.Cin))
+        if choice is not None and choice[0] < 0:              # measured: the fused launch does not beat the two launches' sum
+            return False
+        if choice is None or tuple(choice) not in options:
+            choice = (1 if d.Cout >= 128 else 3, 768)         # 64 x 128 / 64 x 64 tiles, one K tile ahead (two measured 1.5-2x slower)
+            if choice not in options:
+                return False
+        self._lp_state.pop((out.data_ptr(), tuple(out.shape)), None)
+        lst.append(Launch(ops.shortcut_fused_launch, (sc, d, choice[0], choice[1]),
+                          f'{nm}.down+conv3[{d.M}x{d.Cout}x{sc.Cin}+{d.M}x{d.Cout}x{d.Cin}]', 2.0 * d.M * d.Cout * (sc.Cin + d.Cin)))
+        return True
 
     def _resblock(self, lst, rb, x, t, out, N, H, Wd, name):
         # (bf16x3: t feeds conv2 only, through its ReLU -> the image of relu(t) and no f32 tensor)

@@ -224,14 +224,43 @@ def wino_gemm_cfg(tile_cfg, wgs=512):
     return WINO_GEMM_CFG0 + int(tile_cfg) + 8 * (int(wgs) // 128)
 
 
-def wino_gemm_cfg_options(rows_pad, cout):
-    """Every persistent configuration that fits a GEMM with ``rows_pad`` rows per component."""
+# 32-row tiles of the f32 transform-domain GEMM (vfn_winograd_gemm_f32 configurations 8 + tile cfg): ids of their own range, same
+# encoding: id = WINO_GEMM32_CFG0 + tile cfg (& 3: index into WINO_GEMM_TILES32, bit 2: request depth) + 8 * (workgroups / 128)
+WINO_GEMM32_CFG0 = 1500
+WINO_GEMM_TILES32 = ((32, 128, 1, 4), (32, 64, 1, 2))
+
+
+def wino_gemm32_cfg(tile_cfg, wgs=512):
+    assert (int(tile_cfg) & 3) < len(WINO_GEMM_TILES32) and 0 <= int(tile_cfg) < 8
+    return WINO_GEMM32_CFG0 + int(tile_cfg) + 8 * (int(wgs) // 128)
+
+
+def is_wino_gemm32_cfg(cfg):
+    return WINO_GEMM32_CFG0 <= int(cfg) < PCONV_CFG0
+
+
+def persistent_cfg_info(cfg):
+    """(BM, BN, WM, WN, request depth, workgroups) of a persistent configuration id (>= WINO_GEMM_CFG0)."""
+    cfg = int(cfg)
+    c = cfg - (PCONV_CFG0 if cfg >= PCONV_CFG0 else WINO_GEMM32_CFG0 if cfg >= WINO_GEMM32_CFG0 else WINO_GEMM_CFG0)
+    tiles = WINO_GEMM_TILES32 if is_wino_gemm32_cfg(cfg) else WINO_GEMM_TILES
+    return tuple(tiles[c & 3]) + (1 + ((c & 7) >> 2), (c >> 3) * 128)
+
+
+def wino_gemm_cfg_options(rows_pad, cout, rows32=True):
+    """Every persistent configuration that fits a GEMM with ``rows_pad`` rows per component (a 32-row tile only for rows that are a
+    multiple of 32; ``rows32=False``: the 64- and 128-row tiles alone -- what the bf16 form of the kernel has)."""
     out = []
     for tc in range(8):
         bm, bn = WINO_GEMM_TILES[tc & 3][:2]
         if rows_pad % bm or (bn > 64 and cout < 128):
             continue
         out += [wino_gemm_cfg(tc, w) for w in (256, 512, 768)]
+    for tc in (0, 1, 4, 5) if rows32 else ():
+        bm, bn = WINO_GEMM_TILES32[tc & 3][:2]
+        if rows_pad % bm or (bn > 64 and cout < 128):
+            continue
+        out += [wino_gemm32_cfg(tc, w) for w in (256, 512, 768)]
     return out
 
 
@@ -255,6 +284,41 @@ def pconv_eligible(desc, mode=0):
             (not desc.res or (desc.res_mod if desc.res_mod > 0 else desc.M) * desc.res_ld * 4 < lim))
 
 
+def shortcut_fused_eligible(sc, main, mode=0):
+    """Does vfn_conv1x1_shortcut_fused_f32 take this pair (shortcut layer, main layer)?  Mirrors every VFN_ERR_ARG condition of that
+    entry point (csrc/conv_winograd.hip) but the configuration's filter tile (cout_pad: see shortcut_fused_cfg_options)."""
+    lim = 0x7fffff00
+    for d in (sc, main):
+        if (d.KH != 1 or d.KW != 1 or d.pad != 0 or d.mask or d.in_lp or d.out_lp or d.w_packed or d.ksplit > 1 or d.w_batch_rows or d.res or
+                d.Cin < 32 or d.Cin % 32 or d.in_ld < d.Cin or d.in_ld % 4 or d.N < 1 or d.H < 1 or d.W < 1 or not d.inp or not d.w):
+            return False
+    return (mode == 0 and bool(main.out) and main.stride == 1 and sc.stride in (1, 2) and main.M >= 1 and main.M == main.N * main.H * main.W and
+            sc.Ho == (sc.H - 1) // sc.stride + 1 and sc.Wo == (sc.W - 1) // sc.stride + 1 and sc.M == sc.N * sc.Ho * sc.Wo and
+            sc.M == main.M and sc.Cout == main.Cout and main.Cout >= 1 and main.out_ld >= main.Cout and
+            min(sc.cout_pad, main.cout_pad) >= (main.Cout + 63) // 64 * 64 and
+            sc.N * sc.H * sc.W * sc.in_ld * 4 < lim and main.M * main.in_ld * 4 < lim and main.M * main.out_ld * 4 < lim and
+            main.cout_pad * main.Cin * 4 < lim and sc.cout_pad * sc.Cin * 4 < lim)
+
+
+def shortcut_fused_cfg_options(sc, main):
+    """(tile cfg 0..3, workgroups) candidates of the fused launch: the persistent kernel's four tiles (operands one K tile ahead) whose
+    filter tile both layers' padded filter counts cover."""
+    out = []
+    for tc in range(4):
+        bn = WINO_GEMM_TILES[tc & 3][1]
+        if (bn > 64 and main.Cout < 128) or min(sc.cout_pad, main.cout_pad) < (main.Cout + bn - 1) // bn * bn:
+            continue
+        out += [(tc, w) for w in (256, 512, 768)]
+    return out
+
+
+def shortcut_fused_launch(sc, main, tile_cfg, wgs):
+    """The shortcut 1x1 convolution ``sc`` (stride 1 or 2, never written) and the 1x1 convolution ``main`` whose residual it is, as one
+    launch of the persistent kernel (include/vfn_shortcut_fused.h)."""
+    check(_lib.lib().vfn_conv1x1_shortcut_fused_f32(C.byref(sc), C.byref(main), int(tile_cfg), int(wgs), stream()),
+          'vfn_conv1x1_shortcut_fused_f32')
+
+
 def pconv_cfg_options(cout):
     out = []
     for tc in range(8):
@@ -274,6 +338,13 @@ def conv2d_launch(desc, cfg, mode=0):
         return
     if cfg >= WINO_GEMM_CFG0:
         c, rows = cfg - WINO_GEMM_CFG0, desc.w_batch_rows
+        if is_wino_gemm32_cfg(cfg):          # a 32-row tile: native configurations 8 .. 15, f32 only
+            c = cfg - WINO_GEMM32_CFG0
+            if mode != 0 or rows <= 0:
+                raise RuntimeError('the 32-row tiles take an f32 Winograd-domain descriptor (w_batch_rows)')
+            check(_lib.lib().vfn_winograd_gemm_f32(desc.inp, desc.w, desc.out, desc.M // rows, rows, desc.Cin, desc.Cout, desc.cout_pad,
+                                                   8 + (c & 7), (c >> 3) * 128, stream()), 'vfn_winograd_gemm_f32')
+            return
         if mode == 1 and rows > 0:           # plain bf16: the descriptor's `inp` / `w` point at bf16 V / bf16 U (make_winograd_gemm_desc on them)
             check(_lib.lib().vfn_winograd_gemm_bf16(desc.inp, desc.w, desc.out, desc.M // rows, rows, desc.Cin, desc.Cout, desc.cout_pad, c & 7,
                                                     (c >> 3) * 128, stream()), 'vfn_winograd_gemm_bf16')
@@ -291,9 +362,8 @@ def conv_cfg_name(cfg, mode=0, _cache={}):
     """Kernel instantiation behind configuration id ``cfg`` as rocprofv3 prints it (conv_cfg_names + the persistent GEMM ids)."""
     cfg = int(cfg)
     if cfg >= WINO_GEMM_CFG0:
-        c = (cfg - (PCONV_CFG0 if cfg >= PCONV_CFG0 else WINO_GEMM_CFG0)) & 7
-        bm, bn, wm, wn = WINO_GEMM_TILES[c & 3]
-        return f'wino_gemm_kernel<{bm}, {bn}, {wm}, {wn}, {1 + (c >> 2)}, {"true" if cfg >= PCONV_CFG0 else "false"}, {"true" if mode == 1 else "false"}>'
+        bm, bn, wm, wn, pd, _ = persistent_cfg_info(cfg)
+        return f'wino_gemm_kernel<{bm}, {bn}, {wm}, {wn}, {pd}, {"true" if cfg >= PCONV_CFG0 else "false"}, {"true" if mode == 1 else "false"}>'
     if mode not in _cache:
         _cache[mode] = conv_cfg_names(mode)
     return _cache[mode][cfg]
