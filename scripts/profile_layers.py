@@ -35,7 +35,9 @@ for lname, lst in lists.items():
         us = e0.elapsed_time(e1) * 1e3 / reps
         cfg = ''
         if l.fn is ops.conv2d_launch:
-            if l.args[1] >= ops.WINO_GEMM_CFG0:          # the persistent transform-domain GEMM: tile / request depth / workgroups
+            if ops.is_thin3x3_cfg(l.args[1]):            # the LDS-resident 3x3 kernel: 8 x 16 pixel blocks / workgroups
+                cfg = 't8x16/%d' % (ops.thin3x3_cfg_info(l.args[1])[1] or 256)
+            elif l.args[1] >= ops.WINO_GEMM_CFG0:        # the persistent transform-domain GEMM: tile / request depth / workgroups
                 bm_, bn_, _, _, pd_, wgs_ = ops.persistent_cfg_info(l.args[1])
                 cfg = 'p%dx%d/pd%d/%d' % (bm_, bn_, pd_, wgs_)
             else:

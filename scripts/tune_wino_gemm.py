@@ -9,6 +9,9 @@ Writes gpurun_out/tuned_gfx950.json + gpurun_out/r05_tune_{wino_gemm,pconv}_repo
 # configurations -> tuned_gfx950_shortcut.json (a shape whose best fused time does not beat its two launches in
 # scripts/profile_layers.py's table gets tile cfg -1 there by hand: it keeps two launches).  Both write the table and
 # tune_{rows32,shortcut}_report.json into the directory VFN_TUNE_OUT names (default tune_out/, as scripts/tune_winograd.py).
+# Argument `thin3x3`: every 3x3 layer of the inference plans that the LDS-resident kernel takes (ops.thin3x3_eligible: 32 filters, 32 or
+# 64 input channels) through that kernel's grids against the shape's choice in tuned_gfx950.json, each launch repeated in isolation ->
+# tuned_gfx950_thin.json holds the shapes where it is MARGIN faster; tune_thin3x3_report.json lists every shape, won or not.
 import sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, vfloodnet_amd
@@ -105,12 +108,45 @@ def tune_shortcut(plans):
     engine.save_tuned(OUT + '/tuned_gfx950_shortcut.json', 'shortcut')
 
 
+def tune_thin3x3(plans):
+    seen = {}
+    for p in plans:
+        for lst in p.all_lists():
+            for l in lst:
+                if l.fn is ops.conv2d_launch and int(l.args[2]) == 0 and ops.thin3x3_eligible(l.args[0], 0, ignore_split=True):
+                    d = l.args[0]
+                    seen.setdefault((d.M, d.Cout, d.KH * d.KW * d.Cin), (l, p))
+    engine._TUNED_THIN.clear()
+    for key, (l, p) in sorted(seen.items()):
+        d, cur = l.args[0], (l.args[1],)
+        old = tuple(table.get(key) or engine.choose_cfg(*key, 0))
+        t_new = {}
+        for rnd in range(2):                              # alternately with the old choice, the faster of the two rounds each
+            for c in ops.thin3x3_cfg_options(d):
+                ops.set_splitk(d, 1, None)
+                t_new[c] = min(t_new.get(c, 1e30), timeit(d, c))
+            cfg_old = engine.apply_choice(d, old, p.ws, p.cnt)
+            t_old = min(t_old, timeit(d, cfg_old)) if rnd else timeit(d, cfg_old)
+        if ops.is_thin3x3_cfg(cur[0]):                    # leave the plan's descriptor as it was found
+            ops.set_splitk(d, 1, None)
+        best = min((t, c) for c, t in t_new.items())
+        take = best[0] < MARGIN * t_old
+        fl = 2.0 * key[0] * key[1] * key[2]
+        report.append({'layer': l.name, 'shape': list(key), 'old': list(old[:3]), 'old_us': round(t_old, 1), 'old_tf': round(fl / t_old / 1e6, 1),
+                       'thin_us': {ops.thin3x3_cfg_info(c)[1]: round(t, 1) for c, t in sorted(t_new.items())}, 'new': best[1],
+                       'new_us': round(best[0], 1), 'new_tf': round(fl / best[0] / 1e6, 1), 'taken': bool(take)})
+        print(report[-1], flush=True)
+        if take:
+            engine._TUNED_THIN[key] = best[1]
+    engine.save_tuned(OUT + '/tuned_gfx950_thin.json', 'thin')
+
+
 seen = {}
 plans = [eng.plan(h, w, 2) for (h, w) in [(480, 854), (480, 853)]]
-if WHICH in ('rows32', 'shortcut'):
+if WHICH in ('rows32', 'shortcut', 'thin3x3'):
     OUT = os.environ.get('VFN_TUNE_OUT', 'tune_out')
     os.makedirs(OUT, exist_ok=True)
-    (tune_rows32 if WHICH == 'rows32' else tune_shortcut)(plans)
+    {'rows32': tune_rows32, 'shortcut': tune_shortcut, 'thin3x3': tune_thin3x3}[WHICH](plans)
     json.dump(report, open(OUT + '/tune_%s_report.json' % WHICH, 'w'), indent=1)
     sys.exit(0)
 if os.environ.get('VFN_TUNE_TRAIN', '1') == '1':

@@ -142,6 +142,9 @@ with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_image_val.h')) as
 # include/vfn_shortcut_fused.h
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_shortcut_fused.h')) as _f:
     SIGNATURES_SHORTCUT_FUSED = parse_header(_f.read(), STRUCTS)[3]
+# the fifth part (one entry point on vfn_conv_desc): the LDS-resident 3x3 convolution of the 32-filter layers, include/vfn_conv_thin.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_conv_thin.h')) as _f:
+    DEFINES_CONV_THIN, _, _, SIGNATURES_CONV_THIN = parse_header(_f.read(), STRUCTS)
 SEG_SCORES_CHUNK, SEG_SCORES_MAX_BLOCKS = DEFINES_IMAGE_VAL['VFN_SEG_SCORES_CHUNK'], DEFINES_IMAGE_VAL['VFN_SEG_SCORES_MAX_BLOCKS']
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
@@ -200,6 +203,8 @@ def lib():
             declare(name, SIGNATURES_IMAGE_VAL, 'vfn_image_val.h')
         for name in SIGNATURES_SHORTCUT_FUSED:
             declare(name, SIGNATURES_SHORTCUT_FUSED, 'vfn_shortcut_fused.h')
+        for name in SIGNATURES_CONV_THIN:
+            declare(name, SIGNATURES_CONV_THIN, 'vfn_conv_thin.h')
         _lib = L
     return _lib
 

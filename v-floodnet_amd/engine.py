@@ -47,6 +47,11 @@ _TUNED_WINO6_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_wino6
 # shape stays two launches (the fused launch did not beat their sum in scripts/profile_layers.py's tables; entered by hand)
 _TUNED_SHORTCUT = {}
 _TUNED_SHORTCUT_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_shortcut.json')
+# the 32-filter 3x3 layers of the f32 inference plans through the LDS-resident kernel (ops.thin3x3_cfg): (M, Cout, K) -> configuration id,
+# for the shapes where it measured at least 3 % faster in isolation than the choice of tuned_gfx950.json (scripts/tune_wino_gemm.py thin3x3).
+# A table of its own: tuned_gfx950.json serves the training plans and the data-gradient convolutions too, which this kernel does not take
+_TUNED_THIN = {}
+_TUNED_THIN_PATH = _TUNED_PATH.replace('tuned_gfx950.json', 'tuned_gfx950_thin.json')
 
 
 def is_wino6_desc(d):
@@ -81,11 +86,21 @@ def _load_tuned():
     if os.path.isfile(path):
         for k, v in json.load(open(path)).items():
             _TUNED_SHORTCUT[tuple(int(x) for x in k.split(','))] = (int(v[0]), int(v[1]))
+    path = _TUNED_THIN_PATH
+    if alt and os.path.isfile(os.path.join(alt, os.path.basename(path))):
+        path = os.path.join(alt, os.path.basename(path))
+    if os.path.isfile(path):
+        for k, v in json.load(open(path)).items():
+            _TUNED_THIN[tuple(int(x) for x in k.split(','))] = int(v)
 
 
 def save_tuned(path=None, mode=0):
-    """``mode`` = 'wino6': the F(6x6, 3x3) GEMMs' table; 'shortcut': the fused shortcut launches'."""
+    """``mode`` = 'wino6': the F(6x6, 3x3) GEMMs' table; 'shortcut': the fused shortcut launches'; 'thin': the LDS-resident 3x3 kernel's."""
     import json
+    if mode == 'thin':
+        with open(path or _TUNED_THIN_PATH, 'w') as f:
+            json.dump({','.join(str(x) for x in k): int(v) for k, v in sorted(_TUNED_THIN.items())}, f, indent=0)
+        return
     table = _TUNED_WINO6 if mode == 'wino6' else _TUNED_SHORTCUT if mode == 'shortcut' else _TABLES[mode]
     with open(path or (_TUNED_WINO6_PATH if mode == 'wino6' else _TUNED_SHORTCUT_PATH if mode == 'shortcut' else _TABLE_PATHS[mode]), 'w') as f:
         json.dump({','.join(str(x) for x in k): list(v) for k, v in sorted(table.items())}, f, indent=0)
@@ -125,6 +140,12 @@ _WINOGRAD_F6 = os.environ.get('VFN_WINOGRAD_F6', '1')
 _WINO_ROWS32 = os.environ.get('VFN_WINO_ROWS32', '1')
 # a block's shortcut (`down`) convolution inside its conv3's launch in the f32 inference plans (Plan._trunk): 0 = two launches
 _SHORTCUT_FUSED = os.environ.get('VFN_SHORTCUT_FUSED', '1')
+# F(6x6) for an f32 inference layer whose input is a channel slice of a wider tensor (Plan._conv's in_ld: decoder.convFM.q): 0 = the
+# direct launch such layers had before
+_WINO_STRIDED_IN = os.environ.get('VFN_WINO_STRIDED_IN', '1')
+# the LDS-resident 3x3 kernel for the 32-filter layers (csrc/conv_thin3x3.hip) in the f32 inference plans, where
+# tuned_gfx950_thin.json holds the shape: 0 = the tiled launches those layers had before
+_THIN3X3 = os.environ.get('VFN_THIN3X3', '1')
 _WINOGRAD_LP = os.environ.get('VFN_WINOGRAD_LP', '1') == '1'        # Winograd layers in the plain-bf16 mode too (bf16 V / U, vfn_winograd_gemm_bf16)
 _WINOGRAD_MIN_M = int(os.environ.get('VFN_WINOGRAD_MIN_M', 10000))
 _WINO_TABLE = {}
@@ -677,11 +698,14 @@ class FramePlan:
         lp = bf == 2
         if self.eng.mixed:
             f32_out = True                                    # (a consumer in another mode reads the f32 tensor)
-        if ((bf == 0 or (bf == 1 and _WINOGRAD_LP and not self.keep_acts and layer.cin % 64 == 0)) and in_ld is None and
+        if ((bf == 0 or (bf == 1 and _WINOGRAD_LP and not self.keep_acts and layer.cin % 64 == 0)) and
                 (_WINOGRAD_TRAIN or not self.keep_acts) and x.shape[-1] == layer.cin and self.eng.use_winograd(layer, N * H * Wd, bf)):
             tile = 6 if (bf == 0 and not self.keep_acts and res_mod % (H * Wd) == 0 and      # (a residual that repeats per image or not at all)
                          self.eng.winograd_tile(layer, N * H * Wd) == 6) else 4
-            return self._conv_winograd(lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf, tile)
+            # an input that is a channel slice of a wider tensor (in_ld set: decoder.convFM.q reads the value half of the key/value
+            # slab): F(6x6) only -- its input transform walks the pixels at the real stride; F(4x4) and the bf16 modes keep the gate
+            if in_ld is None or (tile == 6 and _WINO_STRIDED_IN != '0' and in_ld % 4 == 0 and in_ld >= layer.cin):
+                return self._conv_winograd(lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf, tile, in_ld)
         d = ops.make_conv_desc(x, layer.w, layer.cout, layer.k, layer.k, layer.stride, layer.pad, out,
                                layer.scale, layer.shift, res, relu_in, relu_out,
                                cin=layer.cin, in_ld=in_ld if in_ld is not None else x.shape[-1],
@@ -697,6 +721,13 @@ class FramePlan:
         else:
             self._lp_state.pop((out.data_ptr(), tuple(out.shape)), None)      # (an f32-only producer: the twin is stale)
         K = layer.k * layer.k * layer.cin
+        thin = _TUNED_THIN.get((d.M, layer.cout, K)) if (bf == 0 and not self.keep_acts and _THIN3X3 != '0') else None
+        if (thin is not None and ops.is_thin3x3_cfg(thin) and ops.thin3x3_cfg_info(thin)[0] == layer.cin and d.res_mod % (H * Wd) == 0 and
+                ops.thin3x3_eligible(d, 0)):
+            # the shipped table holds the shape: the LDS-resident 3x3 kernel (no split-K, no workspace)
+            ops.set_splitk(d, 1, None)
+            lst.append(Launch(ops.conv2d_launch, (d, thin, 0), f'{name}[{d.M}x{layer.cout}x{K}]', 2.0 * d.M * layer.cout * K))
+            return out
         if bf == 1 and layer.cin % 64:                     # (the 32-channel local head: no 64-channel K tile)
             bf = 2
         if bf:
@@ -708,7 +739,7 @@ class FramePlan:
         lst.append(Launch(ops.conv2d_launch, (d, cfg, bf), f'{name}[{d.M}x{layer.cout}x{K}]', 2.0 * d.M * layer.cout * K))
         return out
 
-    def _conv_winograd(self, lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf=0, tile=4):
+    def _conv_winograd(self, lst, layer, x, out, N, H, Wd, res, relu_in, relu_out, name, out_ld, res_mod, bf=0, tile=4, in_ld=None):
         """A 3x3 / stride-1 layer as Winograd F(4x4, 3x3): input transform, the 36 transform-domain GEMMs as ONE batched-filter
         launch of the convolution kernels (tile choice from the same tables / tuner, keyed by the GEMM's shape), output transform
         with the layer's epilogue (csrc/conv_winograd.hip).  ``tile`` = 6 (f32): F(6x6, 3x3), 64 GEMMs over fewer, larger tiles."""
@@ -738,7 +769,8 @@ class FramePlan:
         else:
             V = V[:need_v].view(comps * rows, layer.cin)
             U = layer.w_wino6() if tile == 6 else layer.w_wino()
-        lst.append(Launch(ops.winograd_input, (x, V, rows, relu_in, N, H, Wd, layer.cin, x.shape[-1], tile), name + '.wino_in'))
+        lst.append(Launch(ops.winograd_input, (x, V, rows, relu_in, N, H, Wd, layer.cin, in_ld if in_ld is not None else x.shape[-1], tile),
+                          name + '.wino_in'))
         dg = ops.make_winograd_gemm_desc(V, U, Mb, rows, layer.cin, layer.cout, comps)
         if bf:
             choice = _TABLES[bf].get((dg.M, layer.cout, layer.cin))
@@ -1686,6 +1718,8 @@ class Engine:
                 l_side = id(lst) in side_lists
                 if l.fn is ops.conv2d_launch:
                     d = l.args[0]
+                    if ops.is_thin3x3_cfg(l.args[1]):        # (taken from tuned_gfx950_thin.json: no tuning pass moves it)
+                        continue
                     key = (d.M, d.Cout, d.KH * d.KW * d.Cin, int(l.args[2]), is_wino6_desc(d))
                     if only_missing and key[:3] in table_of(d, key[3]):
                         continue

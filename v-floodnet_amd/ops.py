@@ -328,8 +328,57 @@ def pconv_cfg_options(cout):
     return out
 
 
+# ... and from THIN3X3_CFG0 on: a 3x3 / stride-1 / pad-1 descriptor with 32 filters and 32 or 64 input channels through the LDS-resident
+# kernel (vfn_conv3x3_thin_f32, include/vfn_conv_thin.h): id = THIN3X3_CFG0 + 4096 * (Cin == 32) + workgroups of its persistent grid
+# (0: one per CU) -- the id names the instantiation, as every other id does
+THIN3X3_CFG0 = 3000
+THIN3X3_MAX_WGS = _lib.DEFINES_CONV_THIN['VFN_THIN3X3_MAX_WGS']
+
+
+def thin3x3_cfg(cin, wgs=256):
+    assert cin in (32, 64) and 0 <= int(wgs) <= THIN3X3_MAX_WGS < 4096
+    return THIN3X3_CFG0 + 4096 * (cin == 32) + int(wgs)
+
+
+def is_thin3x3_cfg(cfg):
+    return THIN3X3_CFG0 <= int(cfg) < THIN3X3_CFG0 + 2 * 4096
+
+
+def thin3x3_cfg_info(cfg):
+    """(Cin, workgroups) of a thin-kernel configuration id."""
+    c = int(cfg) - THIN3X3_CFG0
+    return (32 if c >= 4096 else 64), c & 4095
+
+
+def thin3x3_eligible(desc, mode=0, ignore_split=False):
+    """Does vfn_conv3x3_thin_f32 take this descriptor?  Mirrors every VFN_ERR_ARG condition of that entry point (csrc/conv_thin3x3.hip).
+    ``ignore_split``: would it, once the split-K choice of another kernel is cleared (set_splitk(desc, 1, None): the tuning script)."""
+    lim, hw = 0x7fffff00, desc.H * desc.W
+    return (mode == 0 and bool(desc.inp) and bool(desc.w) and bool(desc.out) and desc.KH == 3 and desc.KW == 3 and desc.stride == 1 and
+            desc.pad == 1 and desc.Cout == 32 and desc.cout_pad >= 32 and desc.Cin in (32, 64) and desc.N >= 1 and desc.H >= 1 and
+            desc.W >= 1 and desc.Ho == desc.H and desc.Wo == desc.W and desc.M == desc.N * hw and desc.in_ld >= desc.Cin and
+            desc.in_ld % 4 == 0 and desc.out_ld >= 32 and not desc.mask and not desc.in_lp and not desc.out_lp and not desc.w_packed and
+            not desc.w_batch_rows and (desc.ksplit <= 1 or ignore_split) and
+            (not desc.res or (desc.res_ld >= 32 and desc.res_mod >= 0 and desc.res_mod % hw == 0 and
+                              (desc.res_mod if desc.res_mod > 0 else desc.M) * desc.res_ld * 4 < lim)) and
+            desc.M * desc.in_ld * 4 < lim and desc.M * desc.out_ld * 4 < lim and (desc.inp | desc.w) % 16 == 0)
+
+
+def thin3x3_cfg_options(desc):
+    """Grids the tuner tries: one workgroup per CU, and two where two fit a CU's LDS (Cin 32)."""
+    return [thin3x3_cfg(desc.Cin, w) for w in ((256, 512) if desc.Cin == 32 else (256,))]
+
+
 def conv2d_launch(desc, cfg, mode=0):
     cfg = int(cfg)
+    if is_thin3x3_cfg(cfg):
+        if mode != 0:
+            raise RuntimeError('the LDS-resident 3x3 convolution is an f32 kernel')
+        cin, wgs = thin3x3_cfg_info(cfg)
+        if cin != desc.Cin and desc.Cin in (32, 64):
+            raise RuntimeError(f'configuration {cfg} names the Cin = {cin} instantiation, the layer has Cin = {desc.Cin}')
+        check(_lib.lib().vfn_conv3x3_thin_f32(C.byref(desc), wgs, stream()), 'vfn_conv3x3_thin_f32')
+        return
     if cfg >= PCONV_CFG0:
         c = cfg - PCONV_CFG0
         if mode != 0:
@@ -361,6 +410,8 @@ def conv2d_launch(desc, cfg, mode=0):
 def conv_cfg_name(cfg, mode=0, _cache={}):
     """Kernel instantiation behind configuration id ``cfg`` as rocprofv3 prints it (conv_cfg_names + the persistent GEMM ids)."""
     cfg = int(cfg)
+    if is_thin3x3_cfg(cfg):
+        return f'conv_thin3x3_kernel<{thin3x3_cfg_info(cfg)[0]}>'
     if cfg >= WINO_GEMM_CFG0:
         bm, bn, wm, wn, pd, _ = persistent_cfg_info(cfg)
         return f'wino_gemm_kernel<{bm}, {bn}, {wm}, {wn}, {pd}, {"true" if cfg >= PCONV_CFG0 else "false"}, {"true" if mode == 1 else "false"}>'
@@ -496,7 +547,9 @@ def conv2d_winograd(x, w, scale=None, shift=None, res=None, relu_in=False, relu_
     out = torch.empty(N, H, W, cout, device=x.device, dtype=torch.float32)
     if rows > tiles and tile != 6:                            # (the F(6x6) input transform zeroes its padding rows itself)
         V.view(comps, rows, cin)[:, tiles:].zero_()
-    winograd_input(x, V, rows, relu_in, tile=tile)
+    # (x may be a channel slice of a wider NHWC tensor: the transform walks the pixels at the tensor's own stride)
+    assert x.stride(3) == 1 and x.stride(1) == W * x.stride(2) and x.stride(0) == H * x.stride(1)
+    winograd_input(x, V, rows, relu_in, ld_x=x.stride(2), tile=tile)
     d = make_winograd_gemm_desc(V, U, Mb, rows, cin, cout, comps)
     if conv_cfg_kind(cfg) == 2:
         set_streamk(d, *streamk_scratch(x.device))
