@@ -3,6 +3,8 @@ import pytest
 import torch
 from torch.nn import functional as F
 
+from conv_ref import _reduced_reference
+
 pytestmark = pytest.mark.gpu
 
 # (N, H, W, Cin, Cout, k, stride, relu_in, relu_out, residual)
@@ -90,21 +92,6 @@ BF16_CASES = [
     (2, 7, 11, 1024, 640, 3, 1, False, False, False),
     (1, 33, 47, 64, 96, 3, 1, False, True, True),
 ]
-
-
-def _rb(t):
-    return t.bfloat16().float()
-
-
-def _reduced_reference(x, w, stride, pad, mode):
-    """What the reduced-precision kernels compute, in f64: mode 1 = product of the bf16-rounded operands;
-    mode 2 (bf16x3) = (xh+xl)*(wh+wl) - xl*wl with x = xh + xl + eps split into two bf16."""
-    if mode == 1:
-        return F.conv2d(_rb(x).double(), _rb(w).double(), stride=stride, padding=pad).float()
-    xh, wh = _rb(x), _rb(w)
-    xl, wl = _rb(x - xh), _rb(w - wh)
-    full = F.conv2d((xh.double() + xl.double()), (wh.double() + wl.double()), stride=stride, padding=pad)
-    return (full - F.conv2d(xl.double(), wl.double(), stride=stride, padding=pad)).float()
 
 
 @pytest.mark.parametrize('mode', [1, 2])

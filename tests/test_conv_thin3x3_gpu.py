@@ -111,6 +111,14 @@ def test_thin3x3_honours_the_leading_dimensions(gpu, cin):
     _launch(inner, wp, cin, out, cfg, N, H, W, in_ld=in_ld, out_ld=out_ld, **kw)
     assert torch.equal(out[:, :COUT], y.view(-1, COUT))
     assert bool((buf[:, COUT:] == GUARD).all()) and bool((buf[:W + 16] == GUARD).all()) and bool((buf[W + 16 + M:] == GUARD).all())
+    # the same without any ReLU: a ReLU that dropped a NaN would hide exactly the read the NaN gutters are there to show
+    kw.update(relu_in=False, relu_out=False)
+    y = _launch(xd, wp, cin, torch.empty(N, H, W, COUT, device=gpu), cfg, N, H, W, **kw)
+    assert bool(torch.isfinite(y).all())
+    buf.fill_(GUARD)
+    _launch(inner, wp, cin, out, cfg, N, H, W, in_ld=in_ld, out_ld=out_ld, **kw)
+    assert torch.equal(out[:, :COUT], y.view(-1, COUT))
+    assert bool((buf[:, COUT:] == GUARD).all()) and bool((buf[:W + 16] == GUARD).all()) and bool((buf[W + 16 + M:] == GUARD).all())
 
 
 def test_thin3x3_refuses_what_is_outside_its_domain(gpu):

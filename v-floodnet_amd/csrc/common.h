@@ -42,6 +42,8 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // operand, so under floor = -inf a NaN would leave as -inf and the next layer's ReLU would turn it into 0 -- a diverging
 // training run (the reference's loss.backward() goes NaN) would be kept alive silently.  v_cmp + v_cndmask, no branch.
 __device__ __forceinline__ float vfn_floor_nan(float v, float floor_) { return v < floor_ ? floor_ : v; }
+// The ReLU of the epilogues that are not branch-free: fmaxf's bits for every number (+0 for -0), and a NaN stays a NaN.
+__device__ __forceinline__ float vfn_relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
 // Workgroups are dealt round-robin over the 8 XCDs (a private 4 MiB L2 each).  A kernel whose neighbouring work items read
 // overlapping bytes (window / halo reads: Winograd 6x6 patches, 3x3 pooling windows, bilinear taps) wants NEIGHBOURS ON ONE

@@ -297,7 +297,7 @@ void conv_direct_kernel(const vfn_conv_desc p) {
                 }
                 if (p.relu_out) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                    for (int e = 0; e < 4; ++e) v[e] = vfn_relu_nan(v[e]);
                 }
                 *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.out_ld + col) = v;
             } else {
@@ -309,7 +309,7 @@ void conv_direct_kernel(const vfn_conv_desc p) {
                     if (!p.mask_after && !live) x = 0.f;
                     if (p.res) x += p.res[(size_t)(p.res_mod > 0 ? row % p.res_mod : row) * p.res_ld + c];
                     if (p.mask_after && !live) x = 0.f;
-                    if (p.relu_out) x = fmaxf(x, 0.f);
+                    if (p.relu_out) x = vfn_relu_nan(x);
                     p.out[(size_t)row * p.out_ld + c] = x;
                 }
             }
@@ -383,7 +383,7 @@ __device__ __forceinline__ void wave_epilogue(const vfn_conv_desc& p, float* sC,
                 }
                 if (p.relu_out) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                    for (int e = 0; e < 4; ++e) v[e] = vfn_relu_nan(v[e]);
                 }
                 *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.out_ld + col) = v;
             } else {
@@ -395,7 +395,7 @@ __device__ __forceinline__ void wave_epilogue(const vfn_conv_desc& p, float* sC,
                     if (!p.mask_after && !live) x = 0.f;
                     if (p.res) x += p.res[(size_t)(p.res_mod > 0 ? row % p.res_mod : row) * p.res_ld + c];
                     if (p.mask_after && !live) x = 0.f;
-                    if (p.relu_out) x = fmaxf(x, 0.f);
+                    if (p.relu_out) x = vfn_relu_nan(x);
                     p.out[(size_t)row * p.out_ld + c] = x;
                 }
             }

@@ -100,7 +100,7 @@ __device__ __forceinline__ void splitk_finish(const vfn_conv_desc& p, int* flag,
         }
         if (p.relu_out) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
+            for (int k = 0; k < 4; ++k) v[k] = vfn_relu_nan(v[k]);
         }
         if (p.out) *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.out_ld + col) = v;
         if (p.out_lp) vfn_store_lp4(p.out_lp, row, p.out_ld, col, v, p.out_lp_relu);
@@ -238,7 +238,7 @@ __device__ __forceinline__ bool wide_epilogue(const vfn_conv_desc& p, char* smem
             }
             if (p.relu_out) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = vfn_relu_nan(v[e]);
             }
             if (p.out) *reinterpret_cast<f32x4*>(p.out + (size_t)row * p.out_ld + col) = v;
             if (p.out_lp) vfn_store_lp4(p.out_lp, row, p.out_ld, col, v, p.out_lp_relu);
@@ -435,8 +435,8 @@ __device__ __forceinline__ void conv_igemm_body(const vfn_conv_desc& p) {
                     continue;
                 }
             }
-            v.x = fmaxf(v.x, relu_floor); v.y = fmaxf(v.y, relu_floor);
-            v.z = fmaxf(v.z, relu_floor); v.w = fmaxf(v.w, relu_floor);
+            v.x = vfn_floor_nan(v.x, relu_floor); v.y = vfn_floor_nan(v.y, relu_floor);      // (a NaN stays a NaN: common.h)
+            v.z = vfn_floor_nan(v.z, relu_floor); v.w = vfn_floor_nan(v.w, relu_floor);
             if constexpr (MODE == 1) {
                 const bf16x4 h = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
                 *reinterpret_cast<bf16x4*>(dA + r * BK + ((((c16 >> 1) ^ ((r >> 1) & 7)) << 2) | ((c16 & 1) << 1))) = h;
@@ -679,7 +679,7 @@ __device__ __forceinline__ void conv_igemm_body(const vfn_conv_desc& p) {
                     if (!p.mask_after && !live) v = 0.f;
                     if (p.res) v += p.res[(size_t)(p.res_mod > 0 ? row % p.res_mod : row) * p.res_ld + col];
                     if (p.mask_after && !live) v = 0.f;
-                    if (p.relu_out) v = fmaxf(v, 0.f);
+                    if (p.relu_out) v = vfn_relu_nan(v);
                     p.out[(size_t)row * p.out_ld + col] = v;
                 }
             }
@@ -836,8 +836,8 @@ void conv_igemm_dma_kernel(const vfn_conv_desc p) {
             for (int i = 0; i < TM; ++i) {
                 const int r = i * 32 + li;
                 a[i] = *reinterpret_cast<const f32x4*>(cA + r * BK + ((lc ^ ((r >> 1) & 7)) << 2));
-                a[i].x = fmaxf(a[i].x, relu_floor); a[i].y = fmaxf(a[i].y, relu_floor);
-                a[i].z = fmaxf(a[i].z, relu_floor); a[i].w = fmaxf(a[i].w, relu_floor);
+                a[i].x = vfn_floor_nan(a[i].x, relu_floor); a[i].y = vfn_floor_nan(a[i].y, relu_floor);
+                a[i].z = vfn_floor_nan(a[i].z, relu_floor); a[i].w = vfn_floor_nan(a[i].w, relu_floor);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
@@ -908,7 +908,7 @@ void conv_igemm_dma_kernel(const vfn_conv_desc p) {
                     if (!p.mask_after && !live) v = 0.f;
                     if (p.res) v += p.res[(size_t)(p.res_mod > 0 ? row % p.res_mod : row) * p.res_ld + col];
                     if (p.mask_after && !live) v = 0.f;
-                    if (p.relu_out) v = fmaxf(v, 0.f);
+                    if (p.relu_out) v = vfn_relu_nan(v);
                     p.out[(size_t)row * p.out_ld + col] = v;
                 }
             }
@@ -948,7 +948,7 @@ __global__ void splitk_reduce_kernel(const vfn_conv_desc p, int m_start) {
         }
         if (p.relu_out) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
+            for (int k = 0; k < 4; ++k) v[k] = vfn_relu_nan(v[k]);
         }
         if (p.out) *reinterpret_cast<f32x4*>(p.out + row * p.out_ld + c4 * 4) = v;
         if (p.out_lp) vfn_store_lp4(p.out_lp, row, p.out_ld, c4 * 4, v, p.out_lp_relu);
