@@ -24,6 +24,14 @@ extern "C" {
 int vfn_winograd6_input_f32(const float* x, int N, int H, int W, int C, int ld_x, int relu, float* V, int rows_pad, void* stream);
 int vfn_winograd6_output_f32(const float* Mb, int rows_pad, int N, int H, int W, int Cout, const float* scale, const float* shift,
                              const float* res, int res_ld, int res_mod, int relu_out, float* out, int out_ld, void* stream);
+/* The two transforms exist in two forms that write the same bytes (csrc/conv_winograd.hip): 0 one thread per tile and channel pair,
+ * 2 a tile and channel pair over 8 lanes through LDS (1 named a wave-uniform variant of 0 that was measured out and is not built).
+ * vfn_winograd6_form: the form a call of that shape takes (C: the input transform's C or the output transform's Cout); -1 for a shape
+ * the transforms refuse.  VFN_WINO6_XFORM, read once: 0 / 2 force a form everywhere (1: form 0), unset or "auto" the measured rule.
+ * vfn_winograd6_force_form: the same override inside a process (0 / 1 / 2; 3: the measured rule; -1: back to the environment's
+ * setting). */
+int vfn_winograd6_form(int N, int H, int W, int C, int is_output, int has_res);
+int vfn_winograd6_force_form(int form);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,10 @@ for lname, lst in lists.items():
                 cfg = '%dx%d' % tiles[l.args[1]] + ('/k%d' % l.args[0].ksplit if l.args[0].ksplit > 1 else '') + ('/wk%d' % ops.conv_cfg_wk(l.args[1]) if ops.conv_cfg_wk(l.args[1]) > 1 else '')
         elif l.fn is ops.shortcut_fused_launch:          # a block's shortcut inside conv3's launch: tile / request depth / workgroups
             cfg = 'f%dx%d/pd1/%d' % (ops.WINO_GEMM_TILES[l.args[2]][:2] + (l.args[3],))
+        elif l.fn is ops.winograd_input and l.args[-1] == 6:           # the form of the F(6x6) transform (vfn_winograd6_form)
+            cfg = 'form%d' % ops.winograd6_form(*l.args[4:8], False, False)
+        elif l.fn is ops.winograd_output and l.args[-1] == 6:
+            cfg = 'form%d' % ops.winograd6_form(*l.args[3:7], True, l.args[9] is not None)
         tf = l.flops / us / 1e6 if l.flops else 0
         rows.append((lname, l.name, cfg, us, tf))
         t = tot.setdefault(lname, [0.0, 0.0]); t[0] += us; t[1] += l.flops

@@ -13,6 +13,9 @@
 // the transforms add ~1e-6 relative rounding (tests/test_conv_gpu.py holds it against F.conv2d like every other configuration).
 // Both transforms are HBM-bound: a thread owns 4 channels of one tile, so every load / store of a wave is a contiguous
 // 256-byte to 1-KB row; V and M cost 36/16 of the tensor each way (119 MB each for 2 x 120 x 216 x 256).
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
 #include "common.h"
 #include "conv_internal.h"
 #include "../../include/vfn_hip.h"
@@ -364,6 +367,134 @@ void winograd6_output_kernel(const float* __restrict__ Mb, int rows_pad, int N, 
     }
 }
 
+// ---- the lane-split form of the F(6x6) transforms ("form 2"; vfn_winograd6_form picks a form per call, the kernels above are form 0).
+// Same helpers (bt8 / at8), same order of operations, same epilogue expression: it writes the bytes of form 0
+// (tests/test_winograd6_forms_gpu.py).  A tile and 32 channel pairs per workgroup, a tile-and-pair over 8 lanes: lane j loads column j
+// of the patch (row j of M) and transforms it, the 8x8 goes through LDS transposed (512 B per pair, 16 KB per workgroup), the lane
+// transforms row j (output column j, lanes 0..5) and stores it.  8x the waves of form 0 -- a res4 map is 2000 waves, not 256 -- each
+// with an eighth of the instruction stream (34-46 registers, 8 waves per SIMD); a half-wave's loads and stores are contiguous 256-byte
+// rows.  Tile coordinates come from the workgroup index, so they are scalar; what is per lane is the column j and the channel pair.
+// (Form 1 of the same round -- form 0's thread shape with the tile index through readfirstlane, scalar tap displacements, no per-tap
+// test on inner tiles, 3 waves per SIMD -- was 2-8 % faster than form 0 and slower than this one at every shape but one tie: not kept,
+// DESIGN.md 3.12.)
+constexpr int kW6Oob = 0x7ffffff0;                 // a VGPR offset past every tensor (below 2 GiB): load gives zeros, store is dropped
+
+__device__ __forceinline__ f32x2 w6_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
+    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+}
+__device__ __forceinline__ void w6_store(f32x2 v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
+}
+// the epilogue of winograd6_output_kernel, one pixel of a channel pair
+template <bool RES>
+__device__ __forceinline__ f32x2 w6_epilogue(const f32x2& y, const f32x2& sc, const f32x2& sh, const f32x2& r, float floor_) {
+    f32x2 v;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) v[e] = vfn_floor_nan(y[e] * sc[e] + sh[e] + (RES ? r[e] : 0.f), floor_);
+    return v;
+}
+
+// input.  Grid: rows_pad * ceil(C / 64) workgroups; thread = (j = threadIdx.x / 32: patch column, then V row; threadIdx.x % 32:
+// channel pair of the group).  LDS image [8][8][32] pairs: a wave writes and reads 512 contiguous bytes per access.
+template <bool RELU>
+__global__ __launch_bounds__(256)
+void winograd6_input_split_kernel(const float* __restrict__ x, int N, int H, int W, int C, int ld_x, float* __restrict__ V, int rows_pad) {
+    __shared__ f32x2 lds[64 * 32];
+    const int th = (H + 5) / 6, tw = (W + 5) / 6, tiles = N * th * tw;
+    const int c2n = C / 2, groups = (c2n + 31) / 32;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)((size_t)N * H * W * ld_x * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(V, 0, (int)((size_t)64 * rows_pad * C * 4), 0x00020000);
+    const int comp4 = rows_pad * C * 4;
+    const int blk = (int)vfn_xcd_block(blockIdx.x, gridDim.x);
+    const int tile = blk / groups, cg = blk - tile * groups;
+    const int cp = threadIdx.x & 31, j = threadIdx.x >> 5;
+    const int c2 = cg * 32 + cp;
+    const bool live = c2 < c2n;                               // (C / 2 no multiple of 32: the last group's spare lanes touch no memory)
+    const int vo = live ? (tile * C + c2 * 2) * 4 + j * 8 * comp4 : kW6Oob;      // V: component 8 j of the lane's tile and pair
+    if (tile >= tiles) {                                      // (the whole workgroup)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) w6_store(f32x2{0.f, 0.f}, rv, live ? vo + b * comp4 : kW6Oob, 0);
+        return;
+    }
+    const int tx = tile % tw, ty = (tile / tw) % th, n = tile / (tw * th);
+    const int y0 = 6 * ty - 1, x0 = 6 * tx - 1;
+    const bool colok = live && (unsigned)(x0 + j) < (unsigned)W;
+    const int px4 = ld_x * 4;
+    f32x2 v[8], t[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const bool ok = colok && (unsigned)(y0 + a) < (unsigned)H;
+        v[a] = w6_load(rx, ok ? ((n * H + y0 + a) * W + x0 + j) * px4 + c2 * 8 : kW6Oob, 0);
+    }
+    if constexpr (RELU) {
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) v[a][e] = vfn_floor_nan(v[a][e], 0.f);
+    }
+    bt8(v, t);                                                // column j of B^T d
+#pragma unroll
+    for (int a = 0; a < 8; ++a) lds[(a * 8 + j) * 32 + cp] = t[a];
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < 8; ++b) v[b] = lds[(j * 8 + b) * 32 + cp];
+    bt8(v, t);                                                // row j of (B^T d) B
+#pragma unroll
+    for (int b = 0; b < 8; ++b) w6_store(t[b], rv, live ? vo + b * comp4 : kW6Oob, 0);
+}
+
+// output.  Grid: tiles * ceil(Cout / 64) workgroups; lane j transforms row j of M, then (j < 6) output column j of the tile.
+template <bool RES>
+__global__ __launch_bounds__(256)
+void winograd6_output_split_kernel(const float* __restrict__ Mb, int rows_pad, int N, int H, int W, int Cout,
+                                   const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ res, int res_ld,
+                                   int res_mod, int relu_out, float* __restrict__ out, int out_ld) {
+    __shared__ f32x2 lds[64 * 32];
+    const int th = (H + 5) / 6, tw = (W + 5) / 6;
+    const int c2n = Cout / 2, groups = (c2n + 31) / 32;
+    const int npix = N * H * W;
+    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Mb), 0, (int)((size_t)64 * rows_pad * Cout * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)npix * out_ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? res : Mb), 0,
+                                                                        RES ? (int)((size_t)(res_mod > 0 ? res_mod : npix) * res_ld * 4) : 0, 0x00020000);
+    const float floor_ = relu_out ? 0.f : -INFINITY;
+    const int comp4 = rows_pad * Cout * 4;
+    const int blk = (int)vfn_xcd_block(blockIdx.x, gridDim.x);
+    const int tile = blk / groups, cg = blk - tile * groups;
+    const int cp = threadIdx.x & 31, j = threadIdx.x >> 5;
+    const int c2 = cg * 32 + cp;
+    const bool live = c2 < c2n;
+    const int tx = tile % tw, ty = (tile / tw) % th, n = tile / (tw * th);
+    const int y0 = 6 * ty, x0 = 6 * tx, row0 = (n * H + y0) * W + x0;
+    const bool colok = live && j < 6 && x0 + j < W;           // the lane's output column
+    f32x2 m[8], t[6];
+    const int mo = (tile * Cout + c2 * 2) * 4 + j * 8 * comp4;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) m[b] = w6_load(rm, live ? mo + b * comp4 : kW6Oob, 0);
+    f32x2 rv[6];
+    if constexpr (RES) {
+        // (res_mod: the residual repeats every res_mod pixels, a whole number of images -- a tile never wraps)
+        const int rb = ((row0 + j - (res_mod > 0 ? (n * H * W) / res_mod * res_mod : 0)) * res_ld + c2 * 2) * 4;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) rv[a] = w6_load(rr, colok && y0 + a < H ? rb + a * W * res_ld * 4 : kW6Oob, 0);
+    }
+    f32x2 sc = {1.f, 1.f}, sh = {0.f, 0.f};
+    if (scale && live) sc = *reinterpret_cast<const f32x2*>(scale + c2 * 2);
+    if (shift && live) sh = *reinterpret_cast<const f32x2*>(shift + c2 * 2);
+    at8(m, t);                                                // row j of M A
+#pragma unroll
+    for (int b = 0; b < 6; ++b) lds[(j * 8 + b) * 32 + cp] = t[b];
+    __syncthreads();
+    if (j >= 6) return;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) m[a] = lds[(a * 8 + j) * 32 + cp];
+    at8(m, t);                                                // column j of A^T (M A)
+    const int oo = ((row0 + j) * out_ld + c2 * 2) * 4;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+        w6_store(w6_epilogue<RES>(t[a], sc, sh, rv[a], floor_), ro, colok && y0 + a < H ? oo + a * W * out_ld * 4 : kW6Oob, 0);
+}
+
 // ---- the weight gradient in the transform domain (round 4): dW = G^T [ sum_tiles (B^T d B) (.) (A dY A^T) ] G -- the transposition
 // of the forward algorithm: 36 multiplies per (tile, filter, channel) instead of the direct form's 144.
 //   vfn_winograd_input_f32   V[xi][tile][ci] = (B^T d B)[xi]           (the forward's input transform, ReLU included)
@@ -583,6 +714,40 @@ inline int grid_of(long long total) {
     return (int)(b < 16384 ? (b ? b : 1) : 16384);
 }
 
+// VFN_WINO6_XFORM (read once): 0 = form 0 everywhere, 2 = the lane-split form everywhere (tests), unset or "auto" = the measured rule
+// below; 1 is accepted and means form 0 (the wave-uniform form it named is not in the tree).  vfn_winograd6_force_form overrides it
+// inside a process (tests, scripts/bench_wino6_transforms.py).
+std::atomic<int> g_wino6_forced{-1};
+
+int wino6_env_form() {
+    static const int v = [] {
+        const char* e = getenv("VFN_WINO6_XFORM");
+        if (!e || !*e || !strcmp(e, "auto")) return -1;
+        const int k = atoi(e);
+        return k >= 0 && k <= 2 ? k : -1;
+    }();
+    return v;
+}
+
+// The measured rule (profiles/r11_tune_wino6_transforms.json: each form in isolation at the Winograd shapes of the 480x854 plan, a
+// new form taken where it is >= 3 % faster).  The lane-split form won every input transform and every output transform with a
+// residual; without a residual form 0 stays at the two shapes (tiles, Cout) where the margin was missed.
+int wino6_auto_form(int tiles, int C, bool is_output, bool has_res) {
+    static const int keep0_out[][2] = {{45, 640}, {1440, 256}};
+    if (is_output && !has_res)
+        for (const auto& k : keep0_out)
+            if (tiles == k[0] && C == k[1]) return 0;
+    return 2;
+}
+
+int wino6_form(int N, int H, int W, int C, int is_output, int has_res) {
+    const int forced = g_wino6_forced.load(std::memory_order_relaxed);
+    const int want = forced >= 0 ? forced : wino6_env_form();
+    if (want == 0 || want == 1) return 0;
+    if (want == 2) return 2;                                  // (3, forced: the rule whatever the environment says)
+    return wino6_auto_form(winograd6_tiles(N, H, W), C, is_output != 0, has_res != 0);
+}
+
 }  // namespace
 
 extern "C" int vfn_winograd_tiles(int N, int H, int W) { return N * ((H + 3) / 4) * ((W + 3) / 4); }
@@ -611,9 +776,27 @@ extern "C" int vfn_winograd_output_f32(const float* Mb, int rows_pad, int N, int
 extern "C" int vfn_winograd6_input_f32(const float* x, int N, int H, int W, int C, int ld_x, int relu, float* V, int rows_pad, void* stream) {
     if (!x || !V || N < 1 || H < 1 || W < 1 || C < 4 || C % 4 || ld_x < C || ld_x % 4 || rows_pad < winograd6_tiles(N, H, W)) return VFN_ERR_ARG;
     if (!tensors_fit_32bit(N, H, W, ld_x, 0, 0, 0) || (long long)64 * rows_pad * C * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
-    hipLaunchKernelGGL(winograd6_input_kernel, dim3(((long long)rows_pad * (C / 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, N, H, W, C, ld_x, relu,
-                       V, rows_pad);
+    const hipStream_t s = (hipStream_t)stream;
+    if (wino6_form(N, H, W, C, 0, 0) == 2) {
+        const dim3 grid((long long)rows_pad * ((C / 2 + 31) / 32));
+        if (relu) hipLaunchKernelGGL(winograd6_input_split_kernel<true>, grid, dim3(256), 0, s, x, N, H, W, C, ld_x, V, rows_pad);
+        else hipLaunchKernelGGL(winograd6_input_split_kernel<false>, grid, dim3(256), 0, s, x, N, H, W, C, ld_x, V, rows_pad);
+    } else {
+        hipLaunchKernelGGL(winograd6_input_kernel, dim3(((long long)rows_pad * (C / 2) + 255) / 256), dim3(256), 0, s, x, N, H, W, C, ld_x, relu, V,
+                           rows_pad);
+    }
     return vfn_check_launch();
+}
+
+extern "C" int vfn_winograd6_form(int N, int H, int W, int C, int is_output, int has_res) {
+    if (N < 1 || H < 1 || W < 1 || C < 4 || C % 4) return -1;          // (a form, not a status: 0 is a form)
+    return wino6_form(N, H, W, C, is_output, has_res);
+}
+
+extern "C" int vfn_winograd6_force_form(int form) {
+    if (form < -1 || form > 3) return VFN_ERR_ARG;
+    g_wino6_forced.store(form, std::memory_order_relaxed);
+    return VFN_OK;
 }
 
 extern "C" int vfn_winograd6_output_f32(const float* Mb, int rows_pad, int N, int H, int W, int Cout, const float* scale, const float* shift,
@@ -621,13 +804,13 @@ extern "C" int vfn_winograd6_output_f32(const float* Mb, int rows_pad, int N, in
     if (!Mb || !out || N < 1 || H < 1 || W < 1 || Cout < 4 || Cout % 4 || out_ld < Cout || out_ld % 4 || (res && res_ld % 4) ||
         rows_pad < winograd6_tiles(N, H, W) || res_mod < 0 || (res && res_mod % (H * W))) return VFN_ERR_ARG;
     if (!tensors_fit_32bit(N, H, W, out_ld, res ? res_ld : 0, 0, res_mod) || (long long)64 * rows_pad * Cout * 4 >= 0x7fffff00LL) return VFN_ERR_ARG;
-    const dim3 grid(((long long)winograd6_tiles(N, H, W) * (Cout / 2) + 255) / 256);
-    if (res)
-        hipLaunchKernelGGL(winograd6_output_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift, res, res_ld,
-                           res_mod, relu_out, out, out_ld);
-    else
-        hipLaunchKernelGGL(winograd6_output_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift, res, res_ld,
-                           res_mod, relu_out, out, out_ld);
+    const long long tiles = winograd6_tiles(N, H, W);
+    const int form = wino6_form(N, H, W, Cout, 1, res != nullptr);
+    const dim3 grid(form == 2 ? tiles * ((Cout / 2 + 31) / 32) : (tiles * (Cout / 2) + 255) / 256);
+    auto* kernel = form == 2 ? (res ? winograd6_output_split_kernel<true> : winograd6_output_split_kernel<false>)
+                             : (res ? winograd6_output_kernel<true> : winograd6_output_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, Mb, rows_pad, N, H, W, Cout, scale, shift, res, res_ld, res_mod, relu_out, out,
+                       out_ld);
     return vfn_check_launch();
 }
 

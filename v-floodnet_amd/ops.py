@@ -489,6 +489,12 @@ def winograd6_rows(N, H, W):
     return (winograd6_tiles(N, H, W) + WINO6_ROW_MULT - 1) // WINO6_ROW_MULT * WINO6_ROW_MULT
 
 
+def winograd6_form(N, H, W, C, is_output, has_res):
+    """The form of csrc/conv_winograd.hip that an F(6x6) transform call of this shape takes (0: one thread per tile and channel pair,
+    2: lane-split; VFN_WINO6_XFORM = 0 / 2 forces one, unset the measured rule)."""
+    return _lib.lib().vfn_winograd6_form(N, H, W, C, int(is_output), int(has_res))
+
+
 def pack_winograd_weight_bf16(w):
     """The 36 transform-domain filter banks (pack_winograd_weight: float64 transform) rounded once to bf16: [36 * cout_pad, Cin] bf16."""
     return pack_winograd_weight(w).to(torch.bfloat16).contiguous()
