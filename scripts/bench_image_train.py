@@ -1,0 +1,124 @@
+"""Times of the LinkNet decoder fine-tuning step (vfloodnet_amd/linknet_train.py) on one otherwise idle MI355X, HIP events
+around warmed-up windows:
+
+* ms per ``DecoderTrainer.step`` at 416 x 416, batch 4, beside ``predict_batch`` of the same batch (the inference path, which the
+  training code does not touch: its figure in this tree is the parent commit's), and the ratio of the two;
+* bytes/s of the four BatchNorm kernels on the 86528 x 32 and 10816 x 128 layers (the bytes each must move, computed from the
+  shape), beside a plain float4 copy (``Tensor.copy_``) of the same number of bytes measured in the same run.  The tensors of one
+  timed launch are rotated through a ring larger than the 256 MB last-level cache, so the rates are memory rates.
+
+    python scripts/bench_image_train.py [--out profiles/image_train_step.txt]
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RING_BYTES = 640 * 1024 * 1024
+
+
+def timed(fn, iters, warmup):
+    """Mean milliseconds per call of fn(i) over ``iters`` calls between two events, after ``warmup`` calls."""
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(iters):
+        fn(i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def bench_step(dev, lines, steps, warmup):
+    from tools import synth_linknet
+    from vfloodnet_amd.linknet import LinknetB4
+    from vfloodnet_amd.linknet_train import DecoderTrainer
+    sd = synth_linknet.make_state_dict()
+    x = torch.cat([synth_linknet.frame(50 + i, 416, 416) for i in range(4)]).to(dev)
+    y = (torch.rand(4, 1, 416, 416, generator=torch.Generator().manual_seed(1)) > 0.5).float().to(dev)
+    model = LinknetB4.from_checkpoint(sd, dev)
+    t_pred = timed(lambda i: model.predict_batch(x), steps, max(warmup, 4))          # (the third call captures the graph)
+    trainer = DecoderTrainer(model, init_lr=1e-4)
+    t_step = timed(lambda i: trainer.step(x, y), steps, warmup)
+    spread = [timed(lambda i: trainer.step(x, y), steps, 0) for _ in range(3)]
+    lines.append(f'step 416x416 batch 4: {t_step:.3f} ms per step (three more windows of {steps}: ' + ', '.join(f'{v:.3f}' for v in spread) + ')')
+    lines.append(f'predict_batch 416x416 batch 4 (inference path, unchanged from the parent commit): {t_pred:.3f} ms per call')
+    lines.append(f'ratio step / predict_batch: {t_step / t_pred:.2f}')
+
+
+def bench_bn(dev, lines, iters, warmup):
+    from vfloodnet_amd import _lib as L
+    lib = L.lib()
+    for M, C in ((86528, 32), (10816, 128)):
+        n = M * C
+        ring = max(2, RING_BYTES // (3 * n * 4))
+        xs = [torch.randn(M, C, device=dev) for _ in range(ring)]
+        gs = [1e-4 * torch.randn(M, C, device=dev) for _ in range(ring)]
+        outs = [torch.empty(M, C, device=dev) for _ in range(ring)]
+        gamma, beta = torch.ones(C, device=dev), torch.zeros(C, device=dev)
+        v = {k: torch.zeros(C, device=dev) for k in ('scale', 'shift', 'mean', 'rstd', 'dgamma', 'dbeta', 'rm', 'rv')}
+        part = torch.empty(L.LNT_MAX_BLOCKS * 2 * C, dtype=torch.float64, device=dev)
+        p, s = L.ptr, L.stream()
+
+        def stats(i):
+            L.check(lib.vfn_lnt_bn_stats_f32(p(xs[i % ring]), M, C, C, p(gamma), p(beta), 1e-5, 0.1, p(part), p(v['scale']), p(v['shift']),
+                                             p(v['mean']), p(v['rstd']), p(v['rm']), p(v['rv']), s), 'stats')
+
+        def apply(i):
+            L.check(lib.vfn_lnt_bn_apply_f32(p(xs[i % ring]), p(v['scale']), p(v['shift']), p(outs[i % ring]), M, C, C, C, 1, s), 'apply')
+
+        def bwd_reduce(i):
+            L.check(lib.vfn_lnt_bn_bwd_reduce_f32(p(gs[i % ring]), p(xs[i % ring]), p(v['scale']), p(v['shift']), p(v['mean']), p(v['rstd']), M, C,
+                                                  C, C, 1, p(part), p(v['dgamma']), p(v['dbeta']), s), 'bwd_reduce')
+
+        def bwd_apply(i):
+            L.check(lib.vfn_lnt_bn_bwd_apply_f32(p(gs[i % ring]), p(xs[i % ring]), p(v['scale']), p(v['shift']), p(v['mean']), p(v['rstd']),
+                                                 p(v['dgamma']), p(v['dbeta']), p(outs[i % ring]), M, C, C, C, C, 1, s), 'bwd_apply')
+
+        stats(0)
+        lines.append(f'BatchNorm kernels on {M} x {C} (ring of {ring} tensor sets):')
+        for name, fn, floats in (('stats (2 launches)', stats, n), ('apply', apply, 2 * n), ('bwd_reduce (2 launches)', bwd_reduce, 2 * n),
+                                 ('bwd_apply', bwd_apply, 3 * n)):
+            nbytes = floats * 4
+            ms = timed(fn, iters, warmup)
+            # a copy that moves the same bytes: floats / 2 read and floats / 2 written, slices of the ring's tensors
+            half = floats // 2
+            src = [torch.cat([xs[i], gs[i]]).view(-1)[:half] for i in range(ring)] if half > n else [t.view(-1)[:half] for t in xs]
+            dst = [torch.empty(half, device=dev) for _ in range(ring)]
+            ms_copy = timed(lambda i: dst[i % ring].copy_(src[i % ring]), iters, warmup)
+            lines.append(f'  {name:24s} {nbytes / 1e6:7.2f} MB  {ms * 1e3:8.1f} us  {nbytes / ms / 1e6:8.1f} GB/s   '
+                         f'copy of the same bytes {ms_copy * 1e3:8.1f} us  {nbytes / ms_copy / 1e6:8.1f} GB/s   kernel / copy {ms / ms_copy:.2f}')
+            del src, dst
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--steps', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=200)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_image_train.py measures on the GPU only')
+    dev = torch.device('cuda', 0)
+    lines = [f'{torch.cuda.get_device_name(0)}; HIP events; step windows of {args.steps} after {args.warmup} warm-up steps; '
+             f'kernel windows of {args.iters} launches after 20']
+    with torch.cuda.device(dev):
+        bench_step(dev, lines, args.steps, args.warmup)
+        bench_bn(dev, lines, args.iters, 20)
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
+if __name__ == '__main__':
+    main()

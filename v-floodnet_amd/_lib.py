@@ -145,6 +145,10 @@ with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_shortcut_fused.h'
 # the fifth part (one entry point on vfn_conv_desc): the LDS-resident 3x3 convolution of the 32-filter layers, include/vfn_conv_thin.h
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_conv_thin.h')) as _f:
     DEFINES_CONV_THIN, _, _, SIGNATURES_CONV_THIN = parse_header(_f.read(), STRUCTS)
+# the sixth part (entry points only, no structs): fine-tuning the LinkNet decoder and head, include/vfn_image_train.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_image_train.h')) as _f:
+    DEFINES_IMAGE_TRAIN, _, _, SIGNATURES_IMAGE_TRAIN = parse_header(_f.read())
+LNT_MAX_BLOCKS, LNT_MAX_C = DEFINES_IMAGE_TRAIN['VFN_LNT_MAX_BLOCKS'], DEFINES_IMAGE_TRAIN['VFN_LNT_MAX_C']
 SEG_SCORES_CHUNK, SEG_SCORES_MAX_BLOCKS = DEFINES_IMAGE_VAL['VFN_SEG_SCORES_CHUNK'], DEFINES_IMAGE_VAL['VFN_SEG_SCORES_MAX_BLOCKS']
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
@@ -205,6 +209,8 @@ def lib():
             declare(name, SIGNATURES_SHORTCUT_FUSED, 'vfn_shortcut_fused.h')
         for name in SIGNATURES_CONV_THIN:
             declare(name, SIGNATURES_CONV_THIN, 'vfn_conv_thin.h')
+        for name in SIGNATURES_IMAGE_TRAIN:
+            declare(name, SIGNATURES_IMAGE_TRAIN, 'vfn_image_train.h')
         _lib = L
     return _lib
 
