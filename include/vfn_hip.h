@@ -479,8 +479,13 @@ typedef struct vfn_memread_desc {
     const float* bank_v;   /* [obj][cap][512] */
     const int* bank_len;   /* [obj], device */
     const float* ml;       /* [obj][HW][2] from the mode-0 scan */
-    float* o_part;         /* [obj][nsplit][HW][512] scratch */
-    int* cnt;              /* [obj][stride_cnt] zero-initialised hit counters, or NULL (update_bank=False) */
+    float* o_part;         /* [obj][nsplit][HW][512] scratch: slab sp holds the partial O^T of bank slice sp.  With
+                              nsplit_tail == 0 every query tile (128 columns) is cut into nsplit bank slices and every slab
+                              is written for all HW rows.  With nsplit_tail > 0 tiles 0 .. ceil(HW/128)-2 are cut into
+                              nsplit slices and the LAST tile into nsplit_tail slices (1 <= nsplit_tail <= nsplit, of
+                              ceil(chunks / nsplit_tail) chunks each): slab sp is written for the last tile's rows only
+                              when sp < nsplit_tail, and vfn_memread_finish sums exactly those */
+    int* cnt;             /* [obj][stride_cnt] zero-initialised hit counters, or NULL (update_bank=False) */
     float* info;           /* [obj][cap][2] */
     float* out;            /* [obj][HW][ld_out] decoder input, ld_out >= 1024 (>= 512 when qv is NULL) */
     long long stride_k, stride_v, stride_cnt, stride_info;
@@ -496,6 +501,10 @@ typedef struct vfn_memread_desc {
                               (vfn_bankscan_desc.scores, same layout and stride).  The kernel then runs no score GEMM and
                               touches neither q nor bank_k: bit-identical results (the scan forms the same sums). */
     long long stride_scores;
+    int nsplit_tail;       /* bank slices of the last query tile (see o_part); 0: nsplit, like every other tile.  Non-zero
+                              only with precision 0 and scores (vfn_memread_apply returns VFN_ERR_ARG otherwise, and for
+                              nsplit_tail < 0 or > nsplit); vfn_memread_finish takes it in every precision.  A last tile
+                              with fewer than four live 32-column groups then runs no matrix work on the dead ones */
 } vfn_memread_desc;
 
 /* Round 6, precision 1 (plain bf16) with the kept image (bank_k_lp / bank_v_lp): both entry points select software-pipelined

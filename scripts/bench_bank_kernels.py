@@ -1,14 +1,16 @@
 """Each bank kernel on its own (HIP events) at given bank sizes: scan mode 0 (softmax statistics), apply (P^T V + hit
-counts), finish, scan mode 1 (cosine arg-max).  usage: bench_bank_kernels.py [B ...]   (VFN_LIB_PATH selects a build)"""
+counts), finish, scan mode 1 (cosine arg-max).  usage: bench_bank_kernels.py [B ...]   (VFN_LIB_PATH selects a build)
+NSPLIT / NSPLIT_TAIL fix the apply slices of the full query tiles / of the last tile (vfn_memread_desc.nsplit_tail; f32 with
+stored scores only; unset: pick_apply_split's choice, NSPLIT alone: no tail split); HW the number of query columns."""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, vfloodnet_amd
-from vfloodnet_amd.feature_bank import FeatureBank, pick_nsplit, pick_scan_slices, MAX_SPLIT, MAX_SPLIT_SCAN, QT_SCAN, DK, DV
+from vfloodnet_amd.feature_bank import FeatureBank, pick_nsplit, pick_apply_split, pick_scan_slices, MAX_SPLIT, MAX_SPLIT_SCAN, QT_SCAN, DK, DV
 from vfloodnet_amd import _lib
 from vfloodnet_amd._lib import ptr, stream, check, MemReadDesc, BankScanDesc
 C = _lib.C
 dev = torch.device('cuda', 0)
-HW, K = 1620, 2
+HW, K = int(os.environ.get('HW', 1620)), 2
 PREC = int(os.environ.get('PREC', 0))
 L = _lib.lib()
 
@@ -36,7 +38,11 @@ for B in [int(x) for x in (sys.argv[1:] or ['56000'])]:
     o_part = torch.empty(K, MAX_SPLIT, HW, DV, device=dev); dec_in = torch.empty(K, HW, DV, device=dev)
     nsplit_scan = pick_scan_slices(HW, K, B)
     work = torch.zeros(4, dtype=torch.int32, device=dev)
-    nsplit = min(int(os.environ.get('NSPLIT', 0)), MAX_SPLIT) or pick_nsplit(HW, K, B, QT_SCAN, MAX_SPLIT)   # o_part holds MAX_SPLIT slabs
+    tail_ok = PREC == 0 and os.environ.get('SCORES', '1') != '0'
+    nsplit, nsplit_tail = pick_apply_split(HW, K, B) if tail_ok else (pick_nsplit(HW, K, B, QT_SCAN, MAX_SPLIT), 0)
+    if os.environ.get('NSPLIT'):
+        nsplit = max(1, min(int(os.environ['NSPLIT']), MAX_SPLIT))                                          # o_part holds MAX_SPLIT slabs
+        nsplit_tail = min(int(os.environ.get('NSPLIT_TAIL', 0)), nsplit)
     scale = 1.0 / math.sqrt(DK)
     d = BankScanDesc()
     d.q, d.bank_k, d.bank_len, d.rowscale, d.part = ptr(kv_q), ptr(fb._kbuf), ptr(fb._len_dev), None, ptr(ml_part)
@@ -51,6 +57,8 @@ for B in [int(x) for x in (sys.argv[1:] or ['56000'])]:
         if K * per_obj * 4 < 48 * 2 ** 30:
             scores = torch.empty(K, per_obj, device=dev)
             d.scores, d.stride_scores = ptr(scores), per_obj
+    if scores is None:
+        nsplit_tail = 0
     t_scan0 = timeit(lambda: check(L.vfn_bank_scan(C.byref(d), stream()), 'scan'))
     check(L.vfn_bank_scan_finish(ptr(ml_part), nsplit_scan, HW, K, 0, ptr(ml), None, None, None, stream()), 'fin')
     m = MemReadDesc()
@@ -60,6 +68,7 @@ for B in [int(x) for x in (sys.argv[1:] or ['56000'])]:
     m.stride_k, m.stride_v, m.stride_cnt, m.stride_info = cap * DK, cap * DV, cap, cap * 2
     m.scale, m.thres = scale, 1e-3
     m.ldq, m.ldqv, m.ld_out, m.HW, m.obj_n, m.nsplit, m.precision = DK + DV, DK + DV, DV, HW, K, nsplit, PREC
+    m.nsplit_tail = nsplit_tail
     m.bank_k_lp, m.bank_v_lp = ptr(klp), ptr(vlp)
     if scores is not None:
         m.scores, m.stride_scores = ptr(scores), scores.shape[1]
@@ -77,4 +86,4 @@ for B in [int(x) for x in (sys.argv[1:] or ['56000'])]:
     gf_scan = 2.0 * 128 * B * HW * K / 1e9
     gf_apply = 2.0 * 640 * B * HW * K / 1e9
     print(f'B={B}: scan0 {t_scan0:7.1f} us ({gf_scan / t_scan0 * 1e3:5.1f} TF, nsplit {nsplit_scan})  apply {t_apply:7.1f} us '
-          f'({gf_apply / t_apply * 1e3:5.1f} TF executed, nsplit {nsplit})  finish {t_fin:5.1f} us  scan1 {t_scan1:7.1f} us ({gf_scan / t_scan1 * 1e3:5.1f} TF)')
+          f'({gf_apply / t_apply * 1e3:5.1f} TF executed, nsplit {nsplit} tail {nsplit_tail})  finish {t_fin:5.1f} us  scan1 {t_scan1:7.1f} us ({gf_scan / t_scan1 * 1e3:5.1f} TF)')

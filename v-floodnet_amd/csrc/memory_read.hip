@@ -1685,26 +1685,26 @@ void memread_apply_wide_kernel(const vfn_memread_desc p) {
 // the same products in the same order, so O^T and the hit counts are bit-identical to the recomputing kernel; the frame
 // executes F_min's 1280 B HW FLOP per object for the memory read instead of 1536.
 // LDS: two P^T buffers [128 q][64 b], 64 KB.
-__global__ __launch_bounds__(512, 1)
-void memread_apply_ss_kernel(const vfn_memread_desc p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sP = reinterpret_cast<float*>(smem);      // [128 q][64 b]  (P^T)
-
+// One (bank slice, query tile, object) item of memread_apply_ss_kernel.  LIVE = 32-column groups of the tile that hold query
+// columns (4 except on a last tile cut into its own nsplit_tail slices): groups LIVE..3 get no MFMAs, no P^T fragment reads and
+// no epilogue stores, and the waves that would run their softmax (wq >= LIVE) load no scores -- nobody reads those P^T columns,
+// and their hit counts were 0 (p = 0 exactly past HW).  Per live group the products and their order do not depend on LIVE.
+template <int LIVE>
+__device__ __forceinline__ void apply_ss_item(const vfn_memread_desc& p, float* sP, int split, int nslices, int qt, int obj, int q0, int B) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int wr = wave >> 2, wq = wave & 3;
-    int split, qt, obj, q0, B;
-    apply_slice(p, split, qt, obj, q0, B);
+    const bool smx = LIVE == 4 || wq < LIVE;         // this wave's softmax column block holds query columns (wave-uniform)
     const int qtiles = (p.HW + QTW - 1) / QTW;
     const float* V = p.bank_v + (size_t)obj * p.stride_v;
     const float* S = p.scores + (size_t)obj * p.stride_scores;
 
     int c_lo, c_hi;
-    chunk_range(B, p.nsplit, split, c_lo, c_hi);
+    chunk_range(B, nslices, split, c_lo, c_hi);
 
-    f32x16 o[4][2];                                  // O^T tiles: [query tile][channel tile]
+    f32x16 o[LIVE][2];                               // O^T tiles: [query tile][channel tile]
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < LIVE; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -1762,9 +1762,11 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
         const __amdgpu_buffer_rsrc_t rs0 = chunk_rsrc(c_lo);
         load_v(rs0, 0, 0);
         load_v(rs0, 1, 1);
-        load_scores(c_lo);
-        softmax_to(c_lo, sP);
-        if (c_lo + 1 < c_hi) load_scores(c_lo + 1);
+        if (smx) {
+            load_scores(c_lo);
+            softmax_to(c_lo, sP);
+            if (c_lo + 1 < c_hi) load_scores(c_lo + 1);
+        }
     }
     __syncthreads();                                 // P^T of the first chunk visible
 
@@ -1779,9 +1781,9 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
         const bool nxt = c + 1 < c_hi;
 
         const __amdgpu_buffer_rsrc_t vrsrc = chunk_rsrc(c), vrsrc_n = chunk_rsrc(c + 1);
-        f32x4 a[2][4];                               // P^T fragments, one k-group ahead of their MFMAs
+        f32x4 a[2][LIVE];                            // P^T fragments, one k-group ahead of their MFMAs
 #pragma unroll
-        for (int tq = 0; tq < 4; ++tq) a[0][tq] = *reinterpret_cast<const f32x4*>(sPc + swz64(tq * 32 + li, lh));
+        for (int tq = 0; tq < LIVE; ++tq) a[0][tq] = *reinterpret_cast<const f32x4*>(sPc + swz64(tq * 32 + li, lh));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kk = 0; kk < CH / 8; ++kk) {
@@ -1790,18 +1792,18 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
             else load_v(vrsrc_n, kk + 2 - CH / 8, (kk + 2) % 4);
             if (kk + 1 < CH / 8) {
 #pragma unroll
-                for (int tq = 0; tq < 4; ++tq)
+                for (int tq = 0; tq < LIVE; ++tq)
                     a[(kk + 1) & 1][tq] = *reinterpret_cast<const f32x4*>(sPc + swz64(tq * 32 + li, 2 * (kk + 1) + lh));
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
-                for (int tq = 0; tq < 4; ++tq) {
+                for (int tq = 0; tq < LIVE; ++tq) {
                     o[tq][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk & 1][tq][t], vb[cur][t][0], o[tq][0], 0, 0, 0);
                     o[tq][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk & 1][tq][t], vb[cur][t][1], o[tq][1], 0, 0, 0);
                 }
-            if (kk == 2 && nxt) {
+            if (kk == 2 && nxt && smx) {
                 softmax_to(c + 1, sPn);
                 if (c + 2 < c_hi) load_scores(c + 2);
             }
@@ -1811,7 +1813,7 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
 
     float* dst = p.o_part + ((size_t)obj * p.nsplit + split) * p.HW * DV;
 #pragma unroll
-    for (int tq = 0; tq < 4; ++tq)
+    for (int tq = 0; tq < LIVE; ++tq)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int q = q0 + tq * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -1822,15 +1824,60 @@ void memread_apply_ss_kernel(const vfn_memread_desc p) {
         }
 }
 
+// Workgroup -> item when the last query tile has its own slice count (nsplit_tail > 0): per object nsplit x (qtiles - 1) items
+// of the full tiles, slice-major, then the last tile's nsplit_tail items.  The XCD dealing is apply_item's: an XCD takes a
+// contiguous run of items, so the full tiles of one (object, slice) -- the ones that stream the same value rows -- share an L2;
+// a slice of the last tile covers other rows than any full-tile slice and has no partner to share with.  Bijective for any grid.
+__device__ __forceinline__ void apply_tail_item(const vfn_memread_desc& p, int qtiles, int& split, int& qt, int& obj) {
+    const int per_obj = (int)gridDim.x;              // (qtiles - 1) * nsplit + nsplit_tail
+    int L = (int)blockIdx.x;
+    obj = (int)blockIdx.y;
+    if (!vfn_apply_linear_order) {
+        const int total = (int)(gridDim.x * gridDim.y);
+        const int id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+        const int q = total >> 3, r = total & 7;
+        const int xcd = id & 7, slot = id >> 3;
+        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        obj = L / per_obj;
+        L -= obj * per_obj;
+    }
+    const int full = (qtiles - 1) * p.nsplit;
+    if (L < full) { split = L / (qtiles - 1); qt = L - split * (qtiles - 1); }
+    else { split = L - full; qt = qtiles - 1; }
+}
+
+__global__ __launch_bounds__(512, 1)
+void memread_apply_ss_kernel(const vfn_memread_desc p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* sP = reinterpret_cast<float*>(smem);      // [128 q][64 b]  (P^T)
+    int split, qt, obj, q0, B;
+    if (p.nsplit_tail <= 0) {                        // every tile in nsplit slices, all four column groups computed
+        apply_slice(p, split, qt, obj, q0, B);
+        apply_ss_item<4>(p, sP, split, p.nsplit, qt, obj, q0, B);
+        return;
+    }
+    const int qtiles = (p.HW + QTW - 1) / QTW;
+    apply_tail_item(p, qtiles, split, qt, obj);
+    q0 = qt * QTW;
+    B = p.bank_len[obj];
+    const int live = qt == qtiles - 1 ? (p.HW - q0 + 31) >> 5 : 4;      // workgroup-uniform
+    if (live == 4) apply_ss_item<4>(p, sP, split, qt == qtiles - 1 ? p.nsplit_tail : p.nsplit, qt, obj, q0, B);
+    else if (live == 3) apply_ss_item<3>(p, sP, split, p.nsplit_tail, qt, obj, q0, B);
+    else if (live == 2) apply_ss_item<2>(p, sP, split, p.nsplit_tail, qt, obj, q0, B);
+    else apply_ss_item<1>(p, sP, split, p.nsplit_tail, qt, obj, q0, B);
+}
+
 // out[obj][q][0:512] = sum_split o_part ; out[obj][q][512:1024] = query value; then the hit-count bump
 __global__ void memread_finish_kernel(const vfn_memread_desc p) {
     const int obj = blockIdx.y;
     const size_t total = (size_t)p.HW * (DV / 4);
+    const int last_q0 = (p.HW - 1) / QTW * QTW;      // first row of the last query tile of the apply kernels
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c4 = i % (DV / 4);
         const int q = i / (DV / 4);
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        for (int sp = 0; sp < p.nsplit; ++sp)
+        const int ns = p.nsplit_tail > 0 && q >= last_q0 ? p.nsplit_tail : p.nsplit;      // slabs written for this row
+        for (int sp = 0; sp < ns; ++sp)
             s += *reinterpret_cast<const f32x4*>(p.o_part + (((size_t)obj * p.nsplit + sp) * p.HW + q) * DV + c4 * 4);
         float* o = p.out + ((size_t)obj * p.HW + q) * p.ld_out;
         *reinterpret_cast<f32x4*>(o + c4 * 4) = s;
@@ -1966,6 +2013,8 @@ extern "C" int vfn_memread_apply(const vfn_memread_desc* d, void* stream) {
     if (d->nsplit < 1 || d->ldq % 4) return VFN_ERR_ARG;
     if (d->precision < 0 || d->precision > 2) return VFN_ERR_ARG;
     if (d->scores && !scores_fit(d->stride_scores, d->stride_k, d->HW)) return VFN_ERR_ARG;
+    if (d->nsplit_tail < 0 || d->nsplit_tail > d->nsplit) return VFN_ERR_ARG;
+    if (d->nsplit_tail && !(d->precision == 0 && d->scores)) return VFN_ERR_ARG;      // only the stored-scores f32 kernel knows it
     constexpr size_t LDS_WF = (size_t)(QTW * DK + CH * DK + QTW * CH) * sizeof(float);                       // 128 KB
     constexpr size_t LDS_SS = (size_t)2 * QTW * CH * sizeof(float);                                          // 64 KB
     constexpr size_t LDS_W1 = (size_t)QTW * DK * 2 + (size_t)CH * DK * 4 + 2 * (size_t)QTW * CH * 2;         // 80 KB
@@ -2007,7 +2056,9 @@ extern "C" int vfn_memread_apply(const vfn_memread_desc* d, void* stream) {
     } else {
         kern = memread_apply_shw_kernel<false>; lds = LDS_W1;
     }
-    const dim3 grid(cdiv(d->HW, QTW) * d->nsplit, d->obj_n);
+    // the last query tile in its own number of slices (memread_apply_ss_kernel only): (qtiles - 1) * nsplit + nsplit_tail items
+    const int qtiles = cdiv(d->HW, QTW);
+    const dim3 grid(d->nsplit_tail > 0 ? (qtiles - 1) * d->nsplit + d->nsplit_tail : qtiles * d->nsplit, d->obj_n);
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, *d);
     return vfn_check_launch();
 }
@@ -2016,6 +2067,7 @@ extern "C" int vfn_memread_finish(const vfn_memread_desc* d, void* stream) {
     if (!d || !d->o_part || !d->out || !d->bank_len) return VFN_ERR_ARG;
     if (d->cnt && !d->info) return VFN_ERR_ARG;
     if (d->ld_out % 4 || d->ldqv % 4) return VFN_ERR_ARG;
+    if (d->nsplit_tail < 0 || d->nsplit_tail > d->nsplit) return VFN_ERR_ARG;
     const dim3 grid(1024, d->obj_n);
     hipLaunchKernelGGL(memread_finish_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d);
     return vfn_check_launch();

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, ops, weights as W
 from ._lib import ptr, stream, check, MemReadDesc, BankScanDesc
-from .feature_bank import pick_nsplit, pick_scan_slices, MAX_SPLIT, MAX_SPLIT_SCAN, QT_SCAN, DK, DV
+from .feature_bank import pick_nsplit, pick_apply_split, pick_scan_slices, MAX_SPLIT, MAX_SPLIT_SCAN, QT_SCAN, DK, DV
 
 # (BM, BN) -> relative efficiency of the tile shape in the implicit-GEMM kernel
 _CFG_EFF = {(128, 128): 1.00, (128, 64): 0.95, (64, 128): 0.95, (64, 64): 0.86, (32, 64): 0.74,
@@ -1662,8 +1662,11 @@ class Engine:
         m.scale, m.thres = scale, 1e-3
         m.ldq, m.ldqv, m.ld_out, m.HW, m.obj_n = DK + DV, DK + DV, out.shape[-1], HW, K
         m.precision = mr_mode
-        # 128 query columns per workgroup (8 waves)
-        m.nsplit = pick_nsplit(HW, K, fb.len_upper(), QT_SCAN, MAX_SPLIT)
+        # 128 query columns per workgroup (8 waves); the stored-scores f32 kernel cuts a partial last tile into its own, longer slices
+        if mr_mode == 0 and scores is not None:
+            m.nsplit, m.nsplit_tail = pick_apply_split(HW, K, fb.len_upper())
+        else:
+            m.nsplit = pick_nsplit(HW, K, fb.len_upper(), QT_SCAN, MAX_SPLIT)
         if klp is not None:
             m.bank_k_lp, m.bank_v_lp = ptr(klp), ptr(vlp)
         if scores is not None:

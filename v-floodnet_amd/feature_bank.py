@@ -67,6 +67,56 @@ def pick_nsplit(hw, obj_n, b_upper, qt=QT, max_split=MAX_SPLIT):
     return best
 
 
+# Per-chunk time of a memread_apply_ss_kernel workgroup with `live` 32-column groups on its (last) query tile, as a multiple of
+# live / 4 of a full workgroup's: measured on one-tile launches (HW = 32 live against HW = 128, 20 slices, 57 k and 98 k
+# entries: 0.757 / 0.756, 0.528 / 0.524, 0.308 / 0.306 of the full workgroup's time).  A `live` that is not
+# listed keeps the uniform slicing.
+APPLY_TAIL_WEIGHT = {3: 1.01, 2: 1.05, 1: 1.23}
+CUS = 256
+
+
+def apply_split_cost(hw, obj_n, nchunks, nsplit, nsplit_tail):
+    """Modelled time of the f32 apply launch in units of one 32-column group over one chunk: rounds over the 256 CUs (one
+    workgroup each) x the longest workgroup.  ``nsplit_tail`` = 0: every tile in ``nsplit`` slices at the cost of four groups."""
+    qtiles = (hw + QT_SCAN - 1) // QT_SCAN
+    full = -(-nchunks // nsplit) * 4.0
+    if nsplit_tail == 0:
+        return -(-qtiles * obj_n * nsplit // CUS) * full
+    live = -(-(hw - (qtiles - 1) * QT_SCAN) // 32)
+    tail = -(-nchunks // nsplit_tail) * live * APPLY_TAIL_WEIGHT.get(live, 4.0 / live)
+    wgs = obj_n * ((qtiles - 1) * nsplit + nsplit_tail)
+    return -(-wgs // CUS) * (max(full, tail) if qtiles > 1 else tail)
+
+
+def pick_apply_split(hw, obj_n, b_upper):
+    """(nsplit, nsplit_tail) of the f32 stored-scores apply kernel (vfn_memread_desc): the full query tiles in ``nsplit`` bank
+    slices, a last tile with fewer than four live 32-column groups in ``nsplit_tail`` longer slices that skip the dead groups --
+    the pair of least ``apply_split_cost`` with at least 3 chunks per slice.  Candidates within 1 % of the least cost (and not
+    above the uniform rule's) are ties and go to the fewest slices: (10, 8), one round of 256 workgroups, over (20, 15) / (20, 16)
+    at the C2 sizes -- the frame with its side stream active measured it no slower, alone it is as fast, and the finish kernel
+    reads half the slabs.  No partial last tile, or VFN_APPLY_TAIL=0 (read at every call): ``(pick_nsplit(...),
+    0)``, the rule before the tail split.  VFN_APPLY_SPLIT="s,t" (read at every call) forces a pair, for measurements."""
+    import os
+    nchunks = max(1, (b_upper + CH - 1) // CH)
+    qtiles = (hw + QT_SCAN - 1) // QT_SCAN
+    live = -(-(hw - (qtiles - 1) * QT_SCAN) // 32)
+    uniform = pick_nsplit(hw, obj_n, b_upper, QT_SCAN, MAX_SPLIT)
+    if os.environ.get('VFN_APPLY_TAIL', '1') == '0':
+        return uniform, 0
+    if os.environ.get('VFN_APPLY_SPLIT'):
+        s, t = (int(x) for x in os.environ['VFN_APPLY_SPLIT'].split(','))
+        s = max(1, min(s, MAX_SPLIT))
+        return s, max(0, min(t, s))
+    if live not in APPLY_TAIL_WEIGHT:
+        return uniform, 0
+    smax = max(1, min(nchunks // 3, MAX_SPLIT))
+    cands = [(apply_split_cost(hw, obj_n, nchunks, s, t), s, t) for s in range(1, smax + 1) for t in range(1, s + 1)]
+    least = min(c for c, _, _ in cands)
+    bar = min(1.01 * least, max(least, apply_split_cost(hw, obj_n, nchunks, uniform, 0)))
+    _, s, t = min((c for c in cands if c[0] <= bar), key=lambda c: (c[1], c[0], c[2]))
+    return s, t
+
+
 class FeatureBank:
     def __init__(self, obj_n, memory_budget, device, update_rate=0.1, thres_close=0.95, precision=None):
         self.obj_n = obj_n
