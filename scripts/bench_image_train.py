@@ -8,6 +8,14 @@ around warmed-up windows:
   timed launch are rotated through a ring larger than the 256 MB last-level cache, so the rates are memory rates.
 
     python scripts/bench_image_train.py [--out profiles/image_train_step.txt]
+
+``--mode encoder`` measures the step that trains the encoder as well (``ModelTrainer``, frozen BatchNorm statistics) against the
+decoder-only step and ``predict_batch`` in the same job, the three alternating window by window, and the depthwise data- and
+weight-gradient kernels on the two largest layers (block 2: 144 -> 160 channels, 208 x 208 -> 104 x 104; block 10: 336 -> 352
+channels, 52 x 52 -> 26 x 26; 3 x 3, stride 2, batch 4) beside a copy of the same bytes (a copy of one input-sized tensor,
+scaled to the kernel's byte count):
+
+    python scripts/bench_image_train.py --mode encoder [--out profiles/image_train_encoder_step.txt]
 """
 import argparse
 import os
@@ -97,8 +105,74 @@ def bench_bn(dev, lines, iters, warmup):
             del src, dst
 
 
+def bench_encoder_step(dev, lines, steps, warmup):
+    from tools import synth_linknet
+    from vfloodnet_amd.linknet import LinknetB4
+    from vfloodnet_amd.linknet_train import DecoderTrainer, ModelTrainer
+    sd = synth_linknet.make_state_dict()
+    x = torch.cat([synth_linknet.frame(50 + i, 416, 416) for i in range(4)]).to(dev)
+    y = (torch.rand(4, 1, 416, 416, generator=torch.Generator().manual_seed(1)) > 0.5).float().to(dev)
+    m_full, m_dec, m_pred = (LinknetB4.from_checkpoint(sd, dev) for _ in range(3))
+    full, dec = ModelTrainer(m_full, init_lr=1e-4), DecoderTrainer(m_dec, init_lr=1e-4)
+    sides = (('whole model (encoder on its running statistics)', lambda i: full.step(x, y)), ('decoder and head only', lambda i: dec.step(x, y)),
+             ('predict_batch', lambda i: m_pred.predict_batch(x)))
+    for _, fn in sides:
+        timed(fn, 1, max(warmup, 4))
+    rounds = [[timed(fn, steps, 0) for _, fn in sides] for _ in range(4)]                 # the sides alternate window by window
+    best = [min(r[k] for r in rounds) for k in range(3)]
+    for k, (name, _) in enumerate(sides):
+        lines.append(f'416x416 batch 4, {name}: {best[k]:.3f} ms (four alternating windows of {steps}: ' + ', '.join(f'{r[k]:.3f}' for r in rounds) + ')')
+    lines.append(f'ratio whole-model step / decoder-only step: {best[0] / best[1]:.2f};  whole-model step / predict_batch: {best[0] / best[2]:.2f}')
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        full._pack()
+        full._pack_encoder()
+    b.record()
+    b.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    full.step(x, y)
+    torch.cuda.synchronize()
+    lines.append(f'peak device memory of one whole-model step above what is resident before it: {(torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20:.0f} MiB')
+    lines.append(f'of which packing the filters from the parameters (torch operations on parameter-sized tensors): {a.elapsed_time(b) / steps:.3f} ms')
+
+
+def bench_depthwise(dev, lines, iters, warmup):
+    from vfloodnet_amd import _lib as L
+    lib = L.lib()
+    for name, N, H, C, k, s_ in (('block 2', 4, 208, 160, 3, 2), ('block 10', 4, 52, 352, 3, 2)):
+        Ho = H // s_
+        Mi, Mo = N * H * H, N * Ho * Ho
+        ring = max(2, RING_BYTES // ((2 * Mi + Mo) * C * 4))
+        ys = [torch.randn(Mi, C, device=dev) for _ in range(ring)]
+        gs = [1e-4 * torch.randn(Mo, C, device=dev) for _ in range(ring)]
+        gxs = [torch.empty(Mi, C, device=dev) for _ in range(ring)]
+        w, dw = torch.randn(k * k, C, device=dev), torch.empty(k * k, C, device=dev)
+        part = torch.empty(L.ET_MAX_BLOCKS * k * k * C, dtype=torch.float64, device=dev)
+        p, st = L.ptr, L.stream()
+
+        def dgrad(i):
+            L.check(lib.vfn_et_dw_dgrad_f32(p(gs[i % ring]), p(w), p(ys[i % ring]), p(gxs[i % ring]), N, H, H, C, C, C, C, k, s_, 0, Ho, Ho, 1, st), 'dgrad')
+
+        def wgrad(i):
+            L.check(lib.vfn_et_dw_wgrad_f32(p(gs[i % ring]), p(ys[i % ring]), p(part), p(dw), N, H, H, C, C, C, k, s_, 0, Ho, Ho, 1, st), 'wgrad')
+
+        lines.append(f'depthwise kernels of {name}: {N} x {H} x {H} x {C} -> {Ho} x {Ho}, {k} x {k} / stride {s_}, swish on the input (ring of {ring} tensor sets):')
+        for kname, fn, floats in (('data gradient', dgrad, (Mo + 2 * Mi) * C), ('weight gradient (2 launches)', wgrad, (Mo + Mi) * C)):
+            nbytes = floats * 4
+            ms = timed(fn, iters, warmup)
+            half = min(floats // 2, Mi * C)
+            ms_copy = timed(lambda i: gxs[i % ring].view(-1)[:half].copy_(ys[i % ring].view(-1)[:half]), iters, warmup) * (floats / 2) / half
+            lines.append(f'  {kname:28s} {nbytes / 1e6:7.2f} MB  {ms * 1e3:8.1f} us  {nbytes / ms / 1e6:8.1f} GB/s   '
+                         f'copy of the same bytes {ms_copy * 1e3:8.1f} us  {nbytes / ms_copy / 1e6:8.1f} GB/s   kernel / copy {ms / ms_copy:.2f}')
+        del ys, gs, gxs
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--mode', choices=('decoder', 'encoder'), default='decoder')
     ap.add_argument('--out', default=None)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
@@ -110,8 +184,12 @@ def main():
     lines = [f'{torch.cuda.get_device_name(0)}; HIP events; step windows of {args.steps} after {args.warmup} warm-up steps; '
              f'kernel windows of {args.iters} launches after 20']
     with torch.cuda.device(dev):
-        bench_step(dev, lines, args.steps, args.warmup)
-        bench_bn(dev, lines, args.iters, 20)
+        if args.mode == 'encoder':
+            bench_encoder_step(dev, lines, args.steps, args.warmup)
+            bench_depthwise(dev, lines, min(args.iters, 100), 20)
+        else:
+            bench_step(dev, lines, args.steps, args.warmup)
+            bench_bn(dev, lines, args.iters, 20)
     text = '\n'.join(lines) + '\n'
     print(text, end='')
     if args.out:

@@ -1,10 +1,13 @@
-"""Fine-tuning the bootstrap LinkNet on a labelled set: the training half of ``train_image_seg.py`` on the GPU, with the encoder
-frozen (``linknet_train``; include/vfn_image_train.h holds the definition of ``freeze_encoder=True``).
+"""Fine-tuning the bootstrap LinkNet on a labelled set: the training half of ``train_image_seg.py`` on the GPU
+(``linknet_train``).  ``freeze_encoder`` has three values: ``True`` trains decoder and head (include/vfn_image_train.h holds the
+definition), ``'statistics'`` trains the encoder as well, on its running BatchNorm statistics and without drop-connect
+(include/vfn_encoder_train.h), ``False`` -- the encoder in train mode -- is not built.
 
     TrainEpoch(model, device, optimizer, freeze_encoder=True).run(loader)   smp's TrainEpoch: one pass, the mean logs
     train_model(model, init_lr, num_epochs, out_path, train_loader, val_loader, encoder_name, device)   train_image_seg.py:112-203
 
     python -m vfloodnet_amd.train_image_seg --dataset-path D --encoder efficientnet-b4 --model-path F --freeze-encoder
+    python -m vfloodnet_amd.train_image_seg --dataset-path D --encoder efficientnet-b4 --model-path F --freeze-encoder-statistics
 
 Differences from the reference, on purpose:
 
@@ -13,20 +16,48 @@ Differences from the reference, on purpose:
 * no matplotlib plots;
 * no ImageNet download: ``--model-path`` / ``--resume`` supplies the starting weights (a pickled module, a state dict, or a
   resume checkpoint, whose optimizer state ``--resume`` restores as well);
-* ``freeze_encoder=False`` raises ``NotImplementedError``: batch-statistics BatchNorm, drop-connect, depthwise and squeeze-excite
-  backward in the encoder are not built.
+* ``freeze_encoder=False`` raises ``NotImplementedError``: batch-statistics BatchNorm and drop-connect in the encoder are not built
+  (the depthwise and squeeze-excite backward are: ``freeze_encoder='statistics'``).
 Everything runs on the GPU; there is no CPU fallback.
 """
 import os
 
 import torch
 
-from .linknet_train import Adam, DecoderTrainer, ENCODER_MISSING, freeze_encoder as _freeze
+from .linknet_train import Adam, DecoderTrainer, ENCODER_MISSING, ModelTrainer, UNUSED, freeze_encoder as _freeze, freeze_encoder_statistics
 from .val_image_seg import LOG_ROWS, ValidEpoch, load_checkpoint
 
 ENCODER = 'efficientnet-b4'
 DEFAULT_CHKPT_DIR = os.path.join('./', 'output', 'img_seg_checkpoint')
 LR_SECOND_HALF = 1e-5
+STATISTICS = 'statistics'
+
+
+def _check_mode(freeze_encoder):
+    """True, or 'statistics'; False (the encoder in train mode) is not built."""
+    if freeze_encoder is False or freeze_encoder is None or freeze_encoder == 0:
+        raise NotImplementedError(ENCODER_MISSING)
+    if freeze_encoder is not True and freeze_encoder != STATISTICS:
+        raise ValueError(f"freeze_encoder is True, 'statistics' or False, got {freeze_encoder!r}")
+    return freeze_encoder
+
+
+def new_optimizer(model, freeze_encoder, init_lr):
+    """The mode's ``Adam`` over the model's parameters (the model in that mode)."""
+    if _check_mode(freeze_encoder) == STATISTICS:
+        return Adam(freeze_encoder_statistics(model).named_parameters(), lr=init_lr, skip=UNUSED)
+    return Adam(_freeze(model).named_parameters(), lr=init_lr)
+
+
+def load_optimizer_state(optimizer, sd, freeze_encoder):
+    """``optimizer.load_state_dict(sd)`` for a resume checkpoint; one written in the other mode is refused by name."""
+    n = sum(len(g['params']) for g in sd['param_groups'])
+    if n != optimizer.n_group:
+        mode = lambda k: {52: "freeze_encoder=True (--freeze-encoder)", 468: "freeze_encoder='statistics' (--freeze-encoder-statistics)"}.get(
+            k, 'another model')
+        raise ValueError(f"the checkpoint's optimizer holds {n} parameters: it was written with {mode(n)}; this run trains {optimizer.n_group} "
+                         f'with {mode(optimizer.n_group)}.  Resume in the mode the checkpoint was written in, or start from its weights alone')
+    optimizer.load_state_dict(sd)
 
 
 class TrainEpoch:
@@ -38,13 +69,12 @@ class TrainEpoch:
     epoch: one read-back.  ``log`` keeps it, f64 [batches, 2]."""
 
     def __init__(self, model, device, optimizer=None, freeze_encoder=True, init_lr=1e-4, verbose=True):
-        if not freeze_encoder:
-            raise NotImplementedError(ENCODER_MISSING)
+        mode = _check_mode(freeze_encoder)
         device = torch.device(device)
         if device.type != 'cuda':
             raise RuntimeError('TrainEpoch runs on the GPU only (no CPU fallback)')
         self.model, self.device, self.verbose = model, device, verbose
-        self.trainer = DecoderTrainer(model, init_lr=init_lr, optimizer=optimizer)
+        self.trainer = (ModelTrainer if mode == STATISTICS else DecoderTrainer)(model, init_lr=init_lr, optimizer=optimizer)
         self.optimizer = self.trainer.optimizer
         self.log = None
 
@@ -78,13 +108,12 @@ def train_model(model, init_lr, num_epochs, out_path, train_loader, val_loader, 
     ``score > max_score`` the best model ``model/linknet_<encoder>_epoch_###_score<score>.pth`` (a state dict); at
     ``epoch == int(num_epochs / 2)`` the learning rate drops to 1e-5.  ``train_epoch`` / ``valid_epoch``: objects with
     ``run(loader)`` in place of the two epochs (tests).  Returns the list of (epoch, train logs, valid logs, best or not)."""
-    if not freeze_encoder:
-        raise NotImplementedError(ENCODER_MISSING)
+    _check_mode(freeze_encoder)
     checkpoints_dir, models_dir = os.path.join(out_path, 'checkpoints'), os.path.join(out_path, 'model')
     os.makedirs(checkpoints_dir, exist_ok=True)
     os.makedirs(models_dir, exist_ok=True)
     if train_epoch is None:
-        train_epoch = TrainEpoch(model, device, optimizer, freeze_encoder=True, init_lr=init_lr)
+        train_epoch = TrainEpoch(model, device, optimizer, freeze_encoder=freeze_encoder, init_lr=init_lr)
         optimizer = train_epoch.optimizer
     if valid_epoch is None:
         valid_epoch = ValidEpoch(model, device)
@@ -113,7 +142,8 @@ def train_model(model, init_lr, num_epochs, out_path, train_loader, val_loader, 
 
 def get_args(argv=None):
     import argparse
-    parser = argparse.ArgumentParser(description='Fine-tune the LinkNet decoder and head on the MI355X (train_image_seg.py, encoder frozen).')
+    parser = argparse.ArgumentParser(description='Fine-tune the LinkNet on the MI355X (train_image_seg.py): decoder and head, or the whole '
+                                                 'model with the encoder on its running BatchNorm statistics.')
     parser.add_argument('--dataset-path', type=str, metavar='PATH', required=True,
                         help='Dataset root: train_imgs.txt, JPEGImages/<sub>/*.jpg, Annotations/<sub>/*.png.')
     parser.add_argument('--encoder', type=str, default=ENCODER, help='Encoder name; only efficientnet-b4 is built.')
@@ -124,8 +154,11 @@ def get_args(argv=None):
     parser.add_argument('--out-path', default=DEFAULT_CHKPT_DIR, type=str, metavar='PATH', help='Output folder.')
     parser.add_argument('--model-path', '--resume', dest='model_path', type=str, metavar='PATH', required=True,
                         help='Starting weights: a pickled module, a state dict or a resume checkpoint (no ImageNet download).')
-    parser.add_argument('--freeze-encoder', action='store_true',
-                        help='Train decoder and head only.  Required: training the encoder is not built.')
+    mode = parser.add_mutually_exclusive_group()
+    mode.add_argument('--freeze-encoder', action='store_true', help='Train decoder and head only.')
+    mode.add_argument('--freeze-encoder-statistics', action='store_true',
+                      help='Train the encoder as well, on its running BatchNorm statistics and without drop-connect.  One of the two '
+                           'flags is required: the encoder in train mode is not built.')
     parser.add_argument('--seed', default=0, type=int, help='Seed of the shuffle and the augmentation draws.')
     parser.add_argument('--num-workers', default=4, type=int, help='Loader processes for the host part of the decoding.')
     parser.add_argument('--gpu', default=0, type=int, help='GPU card id.')
@@ -137,8 +170,10 @@ def main(argv=None):
     args = get_args(argv)
     if args.encoder != ENCODER:
         raise ValueError(f'--encoder {args.encoder!r}: only {ENCODER} is built')
-    if not args.freeze_encoder:
-        raise NotImplementedError(ENCODER_MISSING.replace('freeze_encoder=True', '--freeze-encoder'))
+    if not args.freeze_encoder and not args.freeze_encoder_statistics:
+        raise NotImplementedError(ENCODER_MISSING.replace("freeze_encoder='statistics'", '--freeze-encoder-statistics')
+                                  .replace('freeze_encoder=True', '--freeze-encoder'))
+    freeze = STATISTICS if args.freeze_encoder_statistics else True
     if not torch.cuda.is_available() or args.gpu < 0:
         raise ValueError('CUDA is required. --gpu must be >= 0.')
     if args.input_shape < 32 or args.input_shape % 32:
@@ -153,18 +188,17 @@ def main(argv=None):
     train_loader = ImageSampleLoader(train_dataset, device, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, seed=args.seed)
     val_loader = ImageSampleLoader(val_dataset, device, batch_size=1, shuffle=False, num_workers=args.num_workers, seed=args.seed + 1)
     model = load_checkpoint(args.model_path, device)
-    _freeze(model)
-    optimizer = Adam(model.named_parameters(), lr=args.init_lr)
+    optimizer = new_optimizer(model, freeze, args.init_lr)
     start_epoch = 0
     try:
         obj = torch.load(args.model_path, map_location='cpu', weights_only=True)
     except Exception:
         obj = None
     if isinstance(obj, dict) and 'optimizer' in obj and 'weights' in obj:      # a resume checkpoint of train_model
-        optimizer.load_state_dict(obj['optimizer'])
+        load_optimizer_state(optimizer, obj['optimizer'], freeze)
         start_epoch = int(obj.get('epoch', -1)) + 1
     history = train_model(model, args.init_lr, args.epochs, args.out_path, train_loader, val_loader, args.encoder, device,
-                          optimizer=optimizer, start_epoch=start_epoch)
+                          freeze_encoder=freeze, optimizer=optimizer, start_epoch=start_epoch)
     print('Done.')
     return history
 
