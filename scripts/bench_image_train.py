@@ -16,6 +16,13 @@ channels, 52 x 52 -> 26 x 26; 3 x 3, stride 2, batch 4) beside a copy of the sam
 scaled to the kernel's byte count):
 
     python scripts/bench_image_train.py --mode encoder [--out profiles/image_train_encoder_step.txt]
+
+``--mode encoder-bn`` measures the step that trains the encoder in train mode (``FullTrainer``: batch-statistics BatchNorm and
+drop-connect) against the ``'statistics'`` step, the decoder-only step and ``predict_batch`` in the same job, the four alternating
+window by window, and the kernels of include/vfn_encoder_bn_train.h on the expand convolution's output of block 2 (173056 x 160)
+and block 10 (10816 x 352) beside a copy of the same bytes:
+
+    python scripts/bench_image_train.py --mode encoder-bn [--out profiles/image_train_encoder_bn_step.txt]
 """
 import argparse
 import os
@@ -139,6 +146,82 @@ def bench_encoder_step(dev, lines, steps, warmup):
     lines.append(f'of which packing the filters from the parameters (torch operations on parameter-sized tensors): {a.elapsed_time(b) / steps:.3f} ms')
 
 
+def bench_full_step(dev, lines, steps, warmup):
+    from tools import synth_linknet
+    from vfloodnet_amd.linknet import LinknetB4
+    from vfloodnet_amd.linknet_train import DecoderTrainer, FullTrainer, ModelTrainer
+    sd = synth_linknet.make_state_dict()
+    x = torch.cat([synth_linknet.frame(50 + i, 416, 416) for i in range(4)]).to(dev)
+    y = (torch.rand(4, 1, 416, 416, generator=torch.Generator().manual_seed(1)) > 0.5).float().to(dev)
+    m_train, m_stat, m_dec, m_pred = (LinknetB4.from_checkpoint(sd, dev) for _ in range(4))
+    train, stat, dec = FullTrainer(m_train, init_lr=1e-4), ModelTrainer(m_stat, init_lr=1e-4), DecoderTrainer(m_dec, init_lr=1e-4)
+    sides = (('whole model, encoder in train mode (batch statistics, drop-connect drawn per step)', lambda i: train.step(x, y)),
+             ('whole model, encoder on its running statistics', lambda i: stat.step(x, y)), ('decoder and head only', lambda i: dec.step(x, y)),
+             ('predict_batch', lambda i: m_pred.predict_batch(x)))
+    for _, fn in sides:
+        timed(fn, 1, max(warmup, 4))
+    rounds = [[timed(fn, steps, 0) for _, fn in sides] for _ in range(4)]                 # the sides alternate window by window
+    best = [min(r[k] for r in rounds) for k in range(len(sides))]
+    for k, (name, _) in enumerate(sides):
+        lines.append(f'416x416 batch 4, {name}: {best[k]:.3f} ms (four alternating windows of {steps}: ' + ', '.join(f'{r[k]:.3f}' for r in rounds) + ')')
+    lines.append(f"ratio train-mode step / 'statistics' step: {best[0] / best[1]:.2f};  / decoder-only step: {best[0] / best[2]:.2f};  "
+                 f'/ predict_batch: {best[0] / best[3]:.2f}')
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    train.step(x, y)
+    torch.cuda.synchronize()
+    lines.append(f'peak device memory of one train-mode step above what is resident before it: {(torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20:.0f} MiB')
+
+
+def bench_bn_train(dev, lines, iters, warmup):
+    from vfloodnet_amd import _lib as L
+    lib = L.lib()
+    B = 4
+    for name, M, C in (('block 2', 173056, 160), ('block 10', 10816, 352)):
+        n = M * C
+        ring = max(2, RING_BYTES // (3 * n * 4))
+        zs = [torch.randn(M, C, device=dev) for _ in range(ring)]
+        gs = [1e-4 * torch.randn(M, C, device=dev) for _ in range(ring)]
+        ys = [torch.empty(M, C, device=dev) for _ in range(ring)]
+        v = {k: torch.randn(C, device=dev) for k in ('gamma', 'beta', 'rstd', 'nshift', 'fold', 'dbeta', 'dgamma', 'rm', 'rv')}
+        keep = torch.tensor([1.25, 0.0, 1.25, 1.25], device=dev)
+        part = torch.empty(L.ET_MAX_BLOCKS * 2 * C, dtype=torch.float64, device=dev)
+        sg, sga = torch.empty(B, C, device=dev), torch.empty(B, C, device=dev)
+        p, s = L.ptr, L.stream()
+
+        def stats(i):
+            L.check(lib.vfn_et_bn_stats_f32(p(zs[i % ring]), M, C, C, p(v['gamma']), 1e-3, 0.01, p(part), p(v['rstd']), p(v['nshift']), p(v['fold']),
+                                            p(v['rm']), p(v['rv']), C, s), 'stats')
+
+        def norm(i):                                              # as the trainer runs it: xhat in place of z, y beside it
+            L.check(lib.vfn_et_bn_norm_f32(p(zs[i % ring]), p(v['rstd']), p(v['nshift']), p(v['gamma']), p(v['beta']), p(keep), None, p(zs[i % ring]),
+                                           p(ys[i % ring]), B, M // B, C, C, C, C, C, 1, s), 'norm')
+
+        def center(i):                                            # in place, no scale: the expand and depthwise BatchNorms
+            L.check(lib.vfn_et_bn_center_f32(p(gs[i % ring]), p(zs[i % ring]), None, p(v['dbeta']), p(v['dgamma']), p(gs[i % ring]), B, M // B, C, C, C,
+                                             C, s), 'center')
+
+        def center_keep(i):                                       # out of place under the drop-connect scale: the project BatchNorm
+            L.check(lib.vfn_et_bn_center_f32(p(gs[i % ring]), p(zs[i % ring]), p(keep), p(v['dbeta']), p(v['dgamma']), p(ys[i % ring]), B, M // B, C, C,
+                                             C, C, s), 'center')
+
+        def sums(i):
+            L.check(lib.vfn_et_bn_sums_f32(p(sg), p(sga), p(keep), p(v['dbeta']), p(v['dgamma']), B, C, s), 'sums')
+
+        lines.append(f'train-mode BatchNorm kernels on the expand output of {name}: {M} x {C} (ring of {ring} tensor sets):')
+        for kname, fn, floats in (('stats (2 launches)', stats, n), ('norm (xhat in place, y)', norm, 3 * n), ('center in place', center, 3 * n),
+                                  ('center under keep', center_keep, 3 * n)):
+            nbytes = floats * 4
+            ms = timed(fn, iters, warmup)
+            half = min(floats // 2, n)
+            ms_copy = timed(lambda i: ys[i % ring].view(-1)[:half].copy_(gs[i % ring].view(-1)[:half]), iters, warmup) * (floats / 2) / half
+            lines.append(f'  {kname:28s} {nbytes / 1e6:7.2f} MB  {ms * 1e3:8.1f} us  {nbytes / ms / 1e6:8.1f} GB/s   '
+                         f'copy of the same bytes {ms_copy * 1e3:8.1f} us  {nbytes / ms_copy / 1e6:8.1f} GB/s   kernel / copy {ms / ms_copy:.2f}')
+        lines.append(f'  sums under keep ([{B}][{C}], parameter-sized): {timed(sums, iters, warmup) * 1e3:.1f} us')
+        del zs, gs, ys
+
+
 def bench_depthwise(dev, lines, iters, warmup):
     from vfloodnet_amd import _lib as L
     lib = L.lib()
@@ -172,7 +255,7 @@ def bench_depthwise(dev, lines, iters, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--mode', choices=('decoder', 'encoder'), default='decoder')
+    ap.add_argument('--mode', choices=('decoder', 'encoder', 'encoder-bn'), default='decoder')
     ap.add_argument('--out', default=None)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
@@ -184,7 +267,10 @@ def main():
     lines = [f'{torch.cuda.get_device_name(0)}; HIP events; step windows of {args.steps} after {args.warmup} warm-up steps; '
              f'kernel windows of {args.iters} launches after 20']
     with torch.cuda.device(dev):
-        if args.mode == 'encoder':
+        if args.mode == 'encoder-bn':
+            bench_full_step(dev, lines, args.steps, args.warmup)
+            bench_bn_train(dev, lines, min(args.iters, 100), 20)
+        elif args.mode == 'encoder':
             bench_encoder_step(dev, lines, args.steps, args.warmup)
             bench_depthwise(dev, lines, min(args.iters, 100), 20)
         else:

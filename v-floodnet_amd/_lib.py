@@ -153,6 +153,10 @@ LNT_MAX_BLOCKS, LNT_MAX_C = DEFINES_IMAGE_TRAIN['VFN_LNT_MAX_BLOCKS'], DEFINES_I
 with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_encoder_train.h')) as _f:
     DEFINES_ENCODER_TRAIN, _, _, SIGNATURES_ENCODER_TRAIN = parse_header(_f.read())
 ET_MAX_BLOCKS, ET_MAX_SQ = DEFINES_ENCODER_TRAIN['VFN_ET_MAX_BLOCKS'], DEFINES_ENCODER_TRAIN['VFN_ET_MAX_SQ']
+# the eighth part (entry points only, no structs): the encoder in train mode, batch-statistics BatchNorm and drop-connect,
+# include/vfn_encoder_bn_train.h
+with open(os.path.join(os.path.dirname(_HERE), 'include', 'vfn_encoder_bn_train.h')) as _f:
+    SIGNATURES_ENCODER_BN_TRAIN = parse_header(_f.read())[3]
 SEG_SCORES_CHUNK, SEG_SCORES_MAX_BLOCKS = DEFINES_IMAGE_VAL['VFN_SEG_SCORES_CHUNK'], DEFINES_IMAGE_VAL['VFN_SEG_SCORES_MAX_BLOCKS']
 ABI_VERSION = DEFINES['VFN_ABI_VERSION']
 TRAIN_AUG_MAX_T, TRAIN_AUG_MAX_SIDE, TRAIN_AUG_MAX_OUT, TRAIN_AUG_MAX_OBJ = (
@@ -217,6 +221,8 @@ def lib():
             declare(name, SIGNATURES_IMAGE_TRAIN, 'vfn_image_train.h')
         for name in SIGNATURES_ENCODER_TRAIN:
             declare(name, SIGNATURES_ENCODER_TRAIN, 'vfn_encoder_train.h')
+        for name in SIGNATURES_ENCODER_BN_TRAIN:
+            declare(name, SIGNATURES_ENCODER_BN_TRAIN, 'vfn_encoder_bn_train.h')
         _lib = L
     return _lib
 

@@ -35,6 +35,7 @@ from ._lib import ptr, stream, check
 from .engine import choose_cfg, apply_choice, WS_FLOATS
 
 BN_EPS_ENC, BN_EPS_DEC = 1e-3, 1e-5
+BN_MOMENTUM_ENC = 0.01                           # efficientnet_pytorch: 1 - batch_norm_momentum (0.99); the decoder keeps torch's 0.1
 # (repeats, kernel, stride, expand, in, out): EfficientNet-B4 = B0's stages under width 1.4 / depth 1.8 (efficientnet_pytorch/utils.py)
 STAGES = ((2, 3, 1, 1, 48, 24), (4, 3, 2, 6, 24, 32), (4, 5, 2, 6, 32, 56), (6, 3, 2, 6, 56, 112),
           (6, 5, 1, 6, 112, 160), (8, 5, 2, 6, 160, 272), (2, 3, 1, 6, 272, 448))
@@ -69,23 +70,23 @@ class _MBConv(nn.Module):
         oup = b['cin'] * b['e']
         if b['e'] != 1:
             self._expand_conv = nn.Conv2d(b['cin'], oup, 1, bias=False)
-            self._bn0 = nn.BatchNorm2d(oup, eps=BN_EPS_ENC)
+            self._bn0 = nn.BatchNorm2d(oup, eps=BN_EPS_ENC, momentum=BN_MOMENTUM_ENC)
         self._depthwise_conv = nn.Conv2d(oup, oup, b['k'], stride=b['s'], groups=oup, bias=False)
-        self._bn1 = nn.BatchNorm2d(oup, eps=BN_EPS_ENC)
+        self._bn1 = nn.BatchNorm2d(oup, eps=BN_EPS_ENC, momentum=BN_MOMENTUM_ENC)
         self._se_reduce = nn.Conv2d(oup, b['sq'], 1)
         self._se_expand = nn.Conv2d(b['sq'], oup, 1)
         self._project_conv = nn.Conv2d(oup, b['cout'], 1, bias=False)
-        self._bn2 = nn.BatchNorm2d(b['cout'], eps=BN_EPS_ENC)
+        self._bn2 = nn.BatchNorm2d(b['cout'], eps=BN_EPS_ENC, momentum=BN_MOMENTUM_ENC)
 
 
 class _Encoder(nn.Module):
     def __init__(self):
         super().__init__()
         self._conv_stem = nn.Conv2d(3, 48, 3, stride=2, bias=False)
-        self._bn0 = nn.BatchNorm2d(48, eps=BN_EPS_ENC)
+        self._bn0 = nn.BatchNorm2d(48, eps=BN_EPS_ENC, momentum=BN_MOMENTUM_ENC)
         self._blocks = nn.ModuleList([_MBConv(b) for b in _blocks()])
         self._conv_head = nn.Conv2d(448, 1792, 1, bias=False)      # in smp's state dict, not in its encoder's forward
-        self._bn1 = nn.BatchNorm2d(1792, eps=BN_EPS_ENC)
+        self._bn1 = nn.BatchNorm2d(1792, eps=BN_EPS_ENC, momentum=BN_MOMENTUM_ENC)
 
 
 class _DecoderBlock(nn.Module):

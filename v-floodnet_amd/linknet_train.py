@@ -44,8 +44,14 @@ definition and the formulas of one MBConv block's backward; ``freeze_encoder='st
     taps = trainer.encoder_forward(x)             # the stem's and the four stages' features, NHWC, channel-padded
     grads = trainer.encoder_backward(gfeats)      # 413 gradients by state-dict name from the gradients of the five taps
 
-Not built: the encoder in TRAIN mode (batch-statistics BatchNorm and drop-connect there; ``freeze_encoder=False``), graph capture
-of the step, the BatchNorm apply fused into the next convolution's operand read.
+``FullTrainer`` at the end trains the encoder in train mode (include/vfn_encoder_bn_train.h holds that definition;
+``freeze_encoder='train'``): batch-statistics BatchNorm in all 95 encoder BatchNorms, drop-connect in the residual blocks.
+
+    model.train()
+    trainer = FullTrainer(model, init_lr=1e-4, seed=0)
+    logs = trainer.step(x, y)                     # keep=None: the drop-connect scales are drawn from trainer.generator
+
+Not built: graph capture of the step, the BatchNorm apply fused into the next convolution's operand read.
 """
 import torch
 
@@ -57,9 +63,10 @@ from .train import AdamW
 from .val_image_seg import seg_scores
 
 BN_MOMENTUM = 0.1
-ENCODER_MISSING = ('training the encoder in train mode is not built: batch-statistics BatchNorm and drop-connect in the encoder are missing '
-                   "(its depthwise and squeeze-excite backward exist); pass freeze_encoder='statistics' to train it with frozen BatchNorm "
-                   'statistics, or freeze_encoder=True')
+# (freeze_encoder=False is the reference's spelling of 'train'; tests pin its refusal, so making it an alias is a follow-up that edits them)
+ENCODER_MISSING = ("freeze_encoder=False is not accepted: the encoder in train mode (batch-statistics BatchNorm and drop-connect beside its "
+                   "depthwise and squeeze-excite backward) is spelled freeze_encoder='train'; pass freeze_encoder='statistics' to train it with "
+                   'frozen BatchNorm statistics, or freeze_encoder=True')
 # in smp's state dict, not in its encoder's forward: no gradient, no optimizer state, they never move (as under torch's Adam)
 UNUSED = ('encoder._conv_head.weight', 'encoder._bn1.weight', 'encoder._bn1.bias')
 
@@ -427,6 +434,7 @@ class ModelTrainer(DecoderTrainer):
     halves of the encoder's pass on their own: ``encoder_forward`` and ``encoder_backward``."""
 
     _mode = staticmethod(freeze_encoder_statistics)
+    _fold_known = True          # gamma rstd is known before the forward pass (running statistics): the data-gradient filters are packed with it
 
     @staticmethod
     def _new_optimizer(model, init_lr):
@@ -479,10 +487,12 @@ class ModelTrainer(DecoderTrainer):
                     q[key + '_fwd'] = torch.zeros((co_p + 255) // 256 * 256, ci_p, device=dev)
                     q[key + '_dgrad'] = torch.zeros((ci_p + 255) // 256 * 256, co_p, device=dev)
                 q[key + '_fwd'][:w.shape[0], :w.shape[1]] = w.view(w.shape[0], w.shape[1])
-                q[key + '_dgrad'][:ci_p] = (q[key + '_fwd'][:co_p] * bn.fold[:, None]).t()
+                if self._fold_known:
+                    q[key + '_dgrad'][:ci_p] = (q[key + '_fwd'][:co_p] * bn.fold[:, None]).t()
             k2 = q['k'] ** 2
             q['dw_w'][:, :q['oup']] = m._depthwise_conv.weight.detach().view(q['oup'], k2).t()
-            q['dw_fold'] = q['dw_w'] * q['bn1'].fold
+            if self._fold_known:
+                q['dw_fold'] = q['dw_w'] * q['bn1'].fold
             q['se'] = (m._se_reduce.weight.detach().view(q['sq'], q['oup']), m._se_reduce.bias.detach(),
                        m._se_expand.weight.detach().view(q['oup'], q['sq']), m._se_expand.bias.detach())
 
@@ -501,11 +511,13 @@ class ModelTrainer(DecoderTrainer):
         check(_lib.lib().vfn_et_affine_f32(ptr(x), ptr(bn.gamma), ptr(bn.beta), ptr(res), ptr(y), M, C, C, C, C, swish, stream()),
               'vfn_et_affine_f32')
 
-    def _bn_grads(self, grads, bn, g, xh, M, C):
-        """dbeta = sum g, dgamma = sum g xhat."""
+    def _bn_grads(self, grads, bn, g, xh, M, C, keep=None, fresh=False):
+        """dbeta = sum g, dgamma = sum g xhat; -> the gradient the weight and data gradients take under ``bn.fold``: g itself, the
+        statistics are constants here (``keep``, ``fresh``: ``FullTrainer``'s)."""
         check(_lib.lib().vfn_et_colsums_f32(ptr(g), ptr(xh), 1, M, C, C, C, ptr(self.et_part), ptr(bn.dbeta), ptr(bn.dgamma), stream()),
               'vfn_et_colsums_f32')
         grads[bn.name + '.weight'], grads[bn.name + '.bias'] = bn.dgamma[:bn.c].clone(), bn.dbeta[:bn.c].clone()
+        return g
 
     def _wgrad_1x1(self, x, g, cin_p, cout_p, rowscale, N, h, w):
         """[cout_p, cin_p] = diag(rowscale) g^T x over the pixels (a 1x1 convolution does not care how they are arranged; the
@@ -619,11 +631,11 @@ class ModelTrainer(DecoderTrainer):
                 stage -= 1
             name, b1, b2 = q['name'], q['bn1'], q['bn2']
             # the project convolution behind its BatchNorm
-            self._bn_grads(grads, b2, g, S['xh2'], Mo, cout_p)
-            dw = self._wgrad_1x1(S['s'], g, C, cout_p, b2.fold, N, ho, wo)
+            gb = self._bn_grads(grads, b2, g, S['xh2'], Mo, cout_p, keep=S.get('keep'), fresh=True)
+            dw = self._wgrad_1x1(S['s'], gb, C, cout_p, b2.fold, N, ho, wo)
             grads[name + '._project_conv.weight'] = dw[:q['cout'], :q['oup']].unsqueeze(-1).unsqueeze(-1)
             gs = f(N, ho, wo, C)
-            self._conv1x1(g, q['proj_dgrad'], C, gs, None, None, N, ho, wo)
+            self._conv1x1(gb, q['proj_dgrad'], C, gs, None, None, N, ho, wo)
             # squeeze-excite
             dgate, dpool, tmp = f(N, C), f(N, C), f(N * (C + 2 * q['sq']))
             check(L.vfn_et_colsums_f32(ptr(gs), ptr(S['a1']), N, M, C, C, C, ptr(self.et_part), None, ptr(dgate), stream()), 'vfn_et_colsums_f32')
@@ -636,7 +648,7 @@ class ModelTrainer(DecoderTrainer):
             # the gate, the pooling and the swish behind the depthwise BatchNorm: one pass, in place
             check(L.vfn_et_swish_bwd_f32(ptr(gs), ptr(S['gate']), ptr(dpool), 1.0 / M, ptr(S['xh1']), ptr(b1.gamma), ptr(b1.beta), ptr(gs), N, M, C, C,
                                          C, C, stream()), 'vfn_et_swish_bwd_f32')
-            self._bn_grads(grads, b1, gs, S['xh1'], Mo, C)
+            gs = self._bn_grads(grads, b1, gs, S['xh1'], Mo, C)
             # the depthwise convolution
             act = int(q['e'] != 1)
             dwd = f(k * k, C)
@@ -648,7 +660,7 @@ class ModelTrainer(DecoderTrainer):
                                         ho, wo, act, stream()), 'vfn_et_dw_dgrad_f32')
             if act:
                 b0 = q['bn0']
-                self._bn_grads(grads, b0, gy0, S['xh0'], Mi, C)
+                gy0 = self._bn_grads(grads, b0, gy0, S['xh0'], Mi, C)
                 dw = self._wgrad_1x1(S['x'], gy0, q['cin_p'], C, b0.fold, N, h, w)
                 grads[name + '._expand_conv.weight'] = dw[:q['oup'], :q['cin']].unsqueeze(-1).unsqueeze(-1)
                 gx = f(N, h, w, q['cin_p'])
@@ -666,7 +678,7 @@ class ModelTrainer(DecoderTrainer):
         check(L.vfn_ln_add_f32(ptr(g), ptr(t), ptr(g), g.numel(), stream()), 'vfn_ln_add_f32')
         check(L.vfn_et_swish_bwd_f32(ptr(g), None, None, 1.0, ptr(E['xh_stem']), ptr(sb.gamma), ptr(sb.beta), ptr(g), 1, N * h * w, 64, 64, 64, 64,
                                      stream()), 'vfn_et_swish_bwd_f32')
-        self._bn_grads(grads, sb, g, E['xh_stem'], N * h * w, 64)
+        g = self._bn_grads(grads, sb, g, E['xh_stem'], N * h * w, 64)
         dws = f(48, 27)
         check(L.vfn_et_stem_wgrad_f32(ptr(g), ptr(E['x']), ptr(self.et_part), ptr(dws), N, E['H'], E['W'], h, w, 64, _same_pad_before(3, 2), stream()),
               'vfn_et_stem_wgrad_f32')
@@ -685,3 +697,214 @@ class ModelTrainer(DecoderTrainer):
         if feat_grads is not None:
             feat_grads.extend(fg)
         return grads
+
+
+# ------------------------------------------------------------------------------------------------ the encoder in train mode
+DROP_CONNECT_RATE = 0.2          # efficientnet_pytorch: block i of n has rate DROP_CONNECT_RATE * i / n
+
+
+def train_mode(model):
+    """``model.train()`` and a gradient for every parameter: every BatchNorm on batch statistics, drop-connect on."""
+    model.train()
+    for p in model.parameters():
+        p.requires_grad_(True)
+    return model
+
+
+def drop_connect_rates():
+    """(block index, rate) of the blocks that run under drop-connect: residual (stride 1, cin == cout) and rate > 0."""
+    blocks = _blocks()
+    return [(i, DROP_CONNECT_RATE * i / len(blocks)) for i, b in enumerate(blocks) if b['s'] == 1 and b['cin'] == b['cout'] and i > 0]
+
+
+def keep_table(u):
+    """u [blocks under drop-connect][N] uniform in [0, 1) -> the scale of each image's branch: floor(1 - p + u) / (1 - p), that is
+    0 or 1 / (1 - p).  float32."""
+    p = torch.tensor([r for _, r in drop_connect_rates()], dtype=torch.float64)[:, None]
+    if u.dim() != 2 or u.shape[0] != p.shape[0]:
+        raise ValueError(f'expected one row of draws per block under drop-connect ({p.shape[0]}), got {tuple(u.shape)}')
+    return (torch.floor(1.0 - p + u.double()) / (1.0 - p)).float()
+
+
+class FullTrainer(ModelTrainer):
+    """``FullTrainer(model, init_lr, seed=0)``: ``ModelTrainer`` with the encoder in train mode (``freeze_encoder='train'``; the
+    definition heads include/vfn_encoder_bn_train.h): its 95 BatchNorms normalise with the batch's statistics and move their
+    running ones on the device, the residual blocks run under drop-connect.  Each convolution leaves its raw output,
+    ``vfn_et_bn_stats_f32`` writes rstd, -mean rstd and gamma rstd into the BatchNorm table and ``vfn_et_bn_norm_f32`` normalises
+    (xhat in place of the raw output) and applies gamma, beta, the activation, the drop-connect scale and the residual; the
+    backward centres each BatchNorm's gradient (``vfn_et_bn_center_f32``) between the column sums and the weight and data
+    gradients, whose folded filters are formed at the head of the backward, when gamma rstd is known.
+
+    ``keep``: the drop-connect scales [blocks under drop-connect][N] (``keep_table``); None draws them from ``generator``, a host
+    ``torch.Generator`` (``reseed``).  They travel to the device in one pinned asynchronous copy at the head of the step."""
+
+    _mode = staticmethod(train_mode)
+    _fold_known = False
+
+    def __init__(self, model, init_lr=1e-4, optimizer=None, seed=0):
+        super().__init__(model, init_lr=init_lr, optimizer=optimizer)
+        for b in self.bns:
+            m = b.bn
+            if m.momentum is None or not m.track_running_stats or m.running_mean.dtype != torch.float32 or not m.running_mean.is_contiguous():
+                raise ValueError(f'{b.name}: a BatchNorm with a momentum and contiguous float32 running statistics is expected')
+        self.drop = dict(drop_connect_rates())                     # block index -> rate
+        self.drop_row = {i: r for r, i in enumerate(self.drop)}
+        cmax = self.et_part.numel() // (_lib.ET_MAX_BLOCKS * 2)
+        self.ones, self.zeros = torch.ones(cmax, device=self.dev), torch.zeros(cmax, device=self.dev)
+        self.generator = torch.Generator()
+        self.seed = seed
+        self.reseed(0)
+        self._keep_arg, self._keep_host, self._keep_copied = None, None, torch.cuda.Event()
+
+    def reseed(self, epoch):
+        """The drop-connect draws of an epoch follow from (seed, epoch): a resumed run continues the sequence."""
+        self.generator.manual_seed((int(self.seed) * 1000003 + int(epoch)) % (1 << 63))
+
+    # -- what follows the parameters ------------------------------------------------------------------------------------
+    def _pack_bns(self):
+        """gamma and beta only: rstd, -mean rstd and gamma rstd are written by the statistics kernel."""
+        cat = lambda f: torch.cat([f(b.bn).detach().float() for b in self.bns])
+        self.bn_table[:2, self.bn_cols] = torch.stack([cat(lambda m: m.weight), cat(lambda m: m.bias)])
+
+    def _fold(self):
+        """The data-gradient filters (diag(gamma rstd) W)^T and the folded depthwise filter, from the batch's rstd."""
+        for q in self.enc:
+            for key, bn, ci_p, co_p in (('exp', q.get('bn0'), q['cin_p'], q['oup_p']), ('proj', q['bn2'], q['oup_p'], q['cout_p'])):
+                if bn is not None:
+                    q[key + '_dgrad'][:ci_p] = (q[key + '_fwd'][:co_p] * bn.fold[:, None]).t()
+            q['dw_fold'] = q['dw_w'] * q['bn1'].fold
+
+    def _take_keep(self, N):
+        """The step's table on the device, [blocks under drop-connect][N]."""
+        keep, self._keep_arg = self._keep_arg, None
+        R = len(self.drop)
+        if keep is None:
+            keep = keep_table(torch.rand(R, N, generator=self.generator, dtype=torch.float64))
+        if tuple(keep.shape) != (R, N):
+            raise ValueError(f'keep: expected the scales of {R} blocks and {N} images, got {tuple(keep.shape)}')
+        if keep.is_cuda:
+            return keep.to(self.dev, torch.float32).contiguous()
+        if self._keep_host is None or self._keep_host.shape != (R, N):
+            self._keep_host = torch.empty(R, N, dtype=torch.float32, pin_memory=True)
+        self._keep_copied.synchronize()                          # (the last step's copy: long done)
+        self._keep_host.copy_(keep)
+        dev = torch.empty(R, N, dtype=torch.float32, device=self.dev)
+        dev.copy_(self._keep_host, non_blocking=True)
+        self._keep_copied.record()
+        return dev
+
+    # -- launches ---------------------------------------------------------------------------------------------------------
+    def _bn_train(self, bn, z, y, B, M, C, swish=0, keep=None, res=None):
+        """z: the raw convolution output, xhat when this returns; y = act(gamma xhat + beta) keep (+ res)."""
+        L = _lib.lib()
+        m = bn.bn
+        check(L.vfn_et_bn_stats_f32(ptr(z), B * M, C, C, ptr(bn.gamma), m.eps, m.momentum, ptr(self.et_part), ptr(bn.rstd), ptr(bn.nshift),
+                                    ptr(bn.fold), ptr(m.running_mean), ptr(m.running_var), bn.c, stream()), 'vfn_et_bn_stats_f32')
+        check(L.vfn_et_bn_norm_f32(ptr(z), ptr(bn.rstd), ptr(bn.nshift), ptr(bn.gamma), ptr(bn.beta), ptr(keep), ptr(res), ptr(z), ptr(y), B, M, C,
+                                   C, C, C, C, swish, stream()), 'vfn_et_bn_norm_f32')
+
+    def _bn_grads(self, grads, bn, g, xh, M, C, keep=None, fresh=False):
+        """dbeta = sum keep g, dgamma = sum keep g xhat; -> g' = keep g - dbeta / M - xhat dgamma / M: in place, or a new tensor
+        (``fresh``: g is a caller's tensor, or a residual block's pass-through)."""
+        L = _lib.lib()
+        N = self.esaved['N']
+        if keep is None:
+            check(L.vfn_et_colsums_f32(ptr(g), ptr(xh), 1, M, C, C, C, ptr(self.et_part), ptr(bn.dbeta), ptr(bn.dgamma), stream()), 'vfn_et_colsums_f32')
+        else:
+            sg, sga = torch.empty(N, C, device=self.dev), torch.empty(N, C, device=self.dev)
+            check(L.vfn_et_colsums_f32(ptr(g), ptr(xh), N, M // N, C, C, C, ptr(self.et_part), ptr(sg), ptr(sga), stream()), 'vfn_et_colsums_f32')
+            check(L.vfn_et_bn_sums_f32(ptr(sg), ptr(sga), ptr(keep), ptr(bn.dbeta), ptr(bn.dgamma), N, C, stream()), 'vfn_et_bn_sums_f32')
+        grads[bn.name + '.weight'], grads[bn.name + '.bias'] = bn.dgamma[:bn.c].clone(), bn.dbeta[:bn.c].clone()
+        gp = torch.empty_like(g) if fresh or keep is not None else g
+        check(L.vfn_et_bn_center_f32(ptr(g), ptr(xh), ptr(keep), ptr(bn.dbeta), ptr(bn.dgamma), ptr(gp), N, M // N, C, C, C, C, stream()),
+              'vfn_et_bn_center_f32')
+        return gp
+
+    # -- the encoder's two halves -------------------------------------------------------------------------------------------
+    def encoder_forward(self, x, keep=None):
+        """``ModelTrainer.encoder_forward`` in train mode: the running statistics move and the counters count."""
+        self._keep_arg = keep
+        try:
+            taps = super().encoder_forward(x)
+        finally:
+            self._keep_arg = None
+        self._invalidate()
+        return taps
+
+    def _encoder_forward(self, x):
+        L = _lib.lib()
+        N, H, Wd = x.shape[0], x.shape[2], x.shape[3]
+        if N * (H // 32) * (Wd // 32) < 2:         # the deepest BatchNorms see one value per channel: torch's own refusal
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {[N, 448, H // 32, Wd // 32]}')
+        keep = self._take_keep(N)
+        self._pack_encoder()
+        x = x.float().contiguous()
+        f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
+        h, w = H // 2, Wd // 2
+        sb = self.stem_bn
+        xh = f(N, h, w, 64)
+        check(L.vfn_et_stem_f32(ptr(x), ptr(self.stem_w), ptr(self.ones), ptr(self.zeros), ptr(xh), N, H, Wd, h, w, 64, 64, _same_pad_before(3, 2),
+                                stream()), 'vfn_et_stem_f32')
+        cur = f(N, h, w, 64)
+        self._bn_train(sb, xh, cur, N, h * w, 64, swish=1)
+        saved, taps, need = [], [cur], 0
+        for q in self.enc:
+            inp, C = cur, q['oup_p']
+            S = dict(x=inp, h=h, w=w)
+            if q['e'] != 1:
+                S['xh0'] = f(N, h, w, C)
+                self._conv1x1(inp, q['exp_fwd'], C, S['xh0'], None, None, N, h, w)
+                S['y0'] = f(N, h, w, C)
+                self._bn_train(q['bn0'], S['xh0'], S['y0'], N, h * w, C)
+            else:
+                S['y0'] = inp
+            ho, wo = h // q['s'], w // q['s']
+            M = ho * wo
+            S['xh1'] = f(N, ho, wo, C)
+            check(L.vfn_et_dwconv_f32(ptr(S['y0']), ptr(q['dw_w']), ptr(self.ones), ptr(self.zeros), ptr(S['xh1']), N, h, w, C, C, C, q['k'], q['s'],
+                                      q['pad_b'], ho, wo, int(q['e'] != 1), stream()), 'vfn_et_dwconv_f32')
+            S['a1'] = f(N, ho, wo, C)
+            self._bn_train(q['bn1'], S['xh1'], S['a1'], N, M, C, swish=1)
+            S['spx'], S['gate'] = f(N, C), f(N, C)
+            check(L.vfn_et_colsums_f32(ptr(S['a1']), None, N, M, C, C, C, ptr(self.et_part), ptr(S['spx']), None, stream()), 'vfn_et_colsums_f32')
+            w1, c1, w2, c2 = q['se']
+            check(L.vfn_ln_se_gate_batch_f32(ptr(S['spx']), 1, 1.0 / M, ptr(w1), ptr(c1), ptr(w2), ptr(c2), ptr(S['gate']), N, q['oup'], q['sq'], C,
+                                             stream()), 'vfn_ln_se_gate_batch_f32')
+            S['s'] = f(N, ho, wo, C)
+            check(L.vfn_et_scale_rows_f32(ptr(S['a1']), ptr(S['gate']), ptr(S['s']), N, M, C, C, C, stream()), 'vfn_et_scale_rows_f32')
+            S['xh2'] = f(N, ho, wo, q['cout_p'])
+            self._conv1x1(S['s'], q['proj_fwd'], q['cout_p'], S['xh2'], None, None, N, ho, wo)
+            out = f(N, ho, wo, q['cout_p'])
+            if q['i'] in self.drop:
+                S['keep'] = keep[self.drop_row[q['i']]]
+            self._bn_train(q['bn2'], S['xh2'], out, N, M, q['cout_p'], keep=S.get('keep'), res=inp if q['residual'] else None)
+            need = max(need, _chunks(N * h * w, _lib.ET_MAX_BLOCKS) * q['k'] ** 2 * C)
+            saved.append(S)
+            cur, h, w = out, ho, wo
+            if q['i'] + 1 in STAGE_IDXS:
+                taps.append(cur)
+        torch._foreach_add_([b.bn.num_batches_tracked for b in self.bns], 1)
+        if self.wg_part is None or self.wg_part.numel() < need:
+            self.wg_part = torch.empty(need, dtype=torch.float64, device=self.dev)
+        self.esaved = dict(blocks=saved, x=x, xh_stem=xh, N=N, H=H, W=Wd, keep=keep)
+        return taps
+
+    def _encoder_backward(self, gfeats):
+        self._fold()
+        return super()._encoder_backward(gfeats)
+
+    # -- the public steps ----------------------------------------------------------------------------------------------------
+    def forward_backward(self, x, y, feat_grads=None, keep=None):
+        self._keep_arg = keep
+        try:
+            return super().forward_backward(x, y, feat_grads)
+        finally:
+            self._keep_arg = None
+
+    def step(self, x, y, keep=None):
+        """``ModelTrainer.step`` with the step's drop-connect scales (None: drawn from ``generator``)."""
+        self._keep_arg = keep
+        try:
+            return super().step(x, y)
+        finally:
+            self._keep_arg = None
